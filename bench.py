@@ -6,10 +6,17 @@ forward (frozen, pre-trained weights) + kNN prior + DiscreteGraphLearning forwar
 step_loss + gradient all-reduce (N>1) + clip_grad_norm_(3.0) + Adam.
 Prints ONE JSON line (rank 0).  Launch:  python bench.py [--gpus N --steps K --warmup W]
 (for N>1:  python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...).
+Such a plain run does what the headline needs and no more: checkpoint, model, W warm-up steps, K timed steps, the line.  `--dump-outputs DIR`
+adds the arrays the last timed step returned (DIR/<name>.npy); that step then starts from the seeded initial state (InitialState) and the
+checkpoint is a stored one (stored_checkpoint), so two runs, or two builds, compare output for output.
+`--full` adds every other figure named below (the encoder alone, `other_schedule`, `other_input_feed`, `random_init`, the counter passes,
+`other_configs`, the reference's runner loop, `data_parallel`, `cpu_baseline`, `--graph`) after the headline loop; several minutes.
 
 "pre-trained TSFormer_PEMS04.pt loaded" (BASELINE config 2, step/step_arch/step.py:27-35): the checkpoint is produced before the
 timed region by tools/pretrain_checkpoint.py -- `--pretrain-steps` native masked-pre-training steps (the repository's own config-C3
-path) on the same synthetic series -- saved in the reference's format and loaded through `pre_trained_tsformer_path`.  The encoder's
+path) on the same synthetic series -- saved in the reference's format and loaded through `pre_trained_tsformer_path`.  That pre-training
+does not end at the same weights twice (floating-point atomics in its weight gradients), so at the headline config the default checkpoint
+is ONE stored run of the recipe, tests/golden/tsformer_pems04_pretrained.npz (stored_checkpoint; `--fresh-checkpoint` makes it anew).  The encoder's
 softmax schedule is data dependent (units whose scores outrun the fixed shift are redone by the re-shifting loop); the line reports
 how many did (`roofline.fallback_units_per_launch`) and a second figure with random-init weights (`random_init`).
 
@@ -124,6 +131,32 @@ def native_checkpoint(name, cfg, data, steps, dev, workdir):
     return path, {"steps": steps, "batch": 6, "first_loss": losses[0], "last_loss": losses[-1], "seconds": time.perf_counter() - t0, "sd": sd}
 
 
+STORED_CHECKPOINT = {"STEP_PEMS04": (os.path.join(ROOT, "tests", "golden", "tsformer_pems04_pretrained.npz"), 300)}
+
+
+def stored_checkpoint(name, cfg, workdir):
+    """The checkpoint of native_checkpoint(300 steps) at the headline config as ONE stored run of it (tests/golden/tsformer_pems04_pretrained.npz,
+    written by `tools/pretrain_checkpoint.py --pack`): the native pre-training sums its weight gradients with floating-point atomics and two runs
+    of it end at visibly different weights (6 .. 1285 slow-path softmax units per encoder launch from one run to the next), so a checkpoint made
+    in the run is not the same INPUT every run.  The file holds what the frozen forecasting-mode TSFormer reads -- patch embedding, the first P
+    positional rows, the four encoder layers, the encoder norm -- as float16 (the encoder's operand type); the decoder side of the state_dict,
+    which it never reads, is the seeded initialisation.  Returns (path, info) like native_checkpoint."""
+    from step_amd import TSFormer
+    t0 = time.perf_counter()
+    z = np.load(STORED_CHECKPOINT[name][0])
+    torch.manual_seed(0)
+    sd = {k: v.detach().clone() for k, v in TSFormer(**tsformer_args(cfg["L"], "pre-train")).state_dict().items()}
+    for k in z.files:
+        if k.startswith("w."):
+            t = torch.from_numpy(z[k].astype(np.float32))
+            sd[k[2:]][:t.shape[0]] = t
+    path = os.path.join(workdir, "tsformer_ckpt", f"TSFormer_{name.replace('STEP_', '')}.pt")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    torch.save({"model_state_dict": sd}, path)
+    first, last = [float(x) for x in z["losses"]]
+    return path, {"steps": int(z["steps"]), "batch": 6, "first_loss": first, "last_loss": last, "seconds": time.perf_counter() - t0, "sd": sd}
+
+
 def encoder_flops(cfg, B):
     """Algorithmic FLOPs of one encoder launch (SURVEY.md 8d, row T4 + T1): per window
     N*P*(4*(221184 + 384*P) + 2304)."""
@@ -198,7 +231,8 @@ def graph_replay_figure(config, B, ckpt, args, steps=30, timeout=240):
     env = dict(os.environ)
     env.pop("GPU_MAX_HW_QUEUES", None)
     cmd = [sys.executable, os.path.abspath(__file__), "--graph-child", "--config", config, "--batch", str(B), "--steps", str(steps), "--warmup", "8",
-           "--no-extras", "--no-cpu-baseline", "--no-pmc", "--matmul", args.matmul, "--pretrain-steps", "0" if ckpt is None else str(args.pretrain_steps)]
+           "--no-extras", "--no-cpu-baseline", "--no-pmc", "--matmul", args.matmul, "--pretrain-steps", "0" if ckpt is None else str(args.pretrain_steps)] + (
+              ["--fresh-checkpoint"] if args.fresh_checkpoint else [])
     try:
         out = subprocess.run(cmd, env=env, timeout=timeout, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout.decode()
         for line in reversed(out.strip().splitlines()):
@@ -451,6 +485,48 @@ def average_grads(model, params, world):
         off += g.numel()
 
 
+DUMP_MAX_ELEMENTS = 2_000_000          # per array: at most 8 MB of float32, 40 MB over five arrays
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the last timed step handed its caller, one `<name>.npy` per array (float32; python scalars float64).  An array of more
+    than DUMP_MAX_ELEMENTS elements is stored as a fixed sample of them (sorted flat indices drawn from a generator seeded with zero, the same
+    for every build), so that two builds of the project can be compared output for output."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy() if torch.is_tensor(a) else np.asarray(a, dtype=np.float64)
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, DUMP_MAX_ELEMENTS))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
+class InitialState:
+    """--dump-outputs: the trainable parameters, the running statistics and the optimizer as they are before the first step, to be put back
+    before the LAST timed step.  The weight-gradient kernels sum with floating-point atomics, Adam turns a last-bit difference of a near-zero
+    gradient into a step of +-lr, and bf16 operand rounding and the Gumbel sample make such differences discrete: after a few steps two runs
+    of one build hold visibly different parameters (prediction 1.6e-2 apart after 25 steps).  With the state put back, what the last timed step
+    computes depends on the seeds alone, the same every run; it launches the same kernels on the same shapes as every other step, after
+    device-to-device copies of the parameters queued on its stream (no host wait)."""
+
+    def __init__(self, model, params, opt):
+        self.params, self.opt = params, opt
+        self.values = [p.detach().clone() for p in params]
+        self.buffers = [(b, b.detach().clone()) for n, b in model.named_buffers() if "running_" in n or "num_batches_tracked" in n]
+        self.restore()          # (changes nothing here: the copy kernels are loaded before the warm-up, not inside the last timed step)
+
+    @torch.no_grad()
+    def restore(self):
+        torch._foreach_copy_([p.data for p in self.params], self.values)
+        for b, v in self.buffers:
+            b.copy_(v)
+        if hasattr(self.opt, "exp_avg"):          # step_amd.optim.FusedAdamClip
+            self.opt.exp_avg.zero_()
+            self.opt.exp_avg_sq.zero_()
+            self.opt.step_count = 0
+        else:                                     # torch.optim.Adam: moments and step count are created at the next step()
+            self.opt.state.clear()
+
+
 HOST = {"enqueue_s": None}
 
 
@@ -514,7 +590,7 @@ def max_over_ranks(dt, world, dev):
     return dt
 
 
-def pretrain_run(args, cfg, world, rank, dev, warmup, steps):
+def pretrain_run(args, cfg, world, rank, dev, warmup, steps, dump=None):
     """Config C3: one step = TSFormer masked pre-training forward + masked_mae + backward + clip(5.0) + Adam
     (reference step/TSFormer_PEMS-BAY.py:52-72), windows/s = sequences of L steps x N nodes per second."""
     import random
@@ -544,9 +620,16 @@ def pretrain_run(args, cfg, world, rank, dev, warmup, steps):
         ts = rng.integers(Lh, cfg["T_all"] - 12, size=B)
         batches.append(torch.stack([dser[t - Lh:t] for t in ts]))
 
+    last = {}
+    state0 = InitialState(model, params, opt) if dump else None
+
     def step(i):
+        if dump and i == warmup + steps - 1:
+            state0.restore()
         opt.zero_grad(set_to_none=True)
         recon, label = model(history_data=batches[i % len(batches)], future_data=None, batch_seen=i, epoch=1)
+        if dump:
+            last.update(reconstruction=recon.detach(), label=label.detach())
         if args.torch_optim:
             loss = masked_mae(recon * 150.0 + 200.0, label * 150.0 + 200.0, 0.0)
         else:
@@ -563,6 +646,8 @@ def pretrain_run(args, cfg, world, rank, dev, warmup, steps):
             torch.distributed.barrier()
         torch.cuda.synchronize()
     dt, per_step, loss = timed_loop(step, warmup, steps, barrier)
+    if dump and rank == 0:
+        dump_outputs(dump, dict(last, loss=loss))
     dt = max_over_ranks(dt, world, dev)
     flops = B * 87.2e9
     return {"value": B * world * steps / dt, "unit": "windows/s", "ms_per_step": dt / steps * 1e3, "steps": steps, "warmup": warmup,
@@ -632,6 +717,10 @@ class StepBench:
         self._staged = None
         self._announced = None
         self._pin = None
+        self.keep_outputs = bool(getattr(args, "dump_outputs", None))
+        self.state0 = InitialState(self.model, self.params, self.opt) if self.keep_outputs and not args.forward_only else None
+        self.restore_at = None          # run(): index of the last timed step of the headline loop
+        self.last = {}          # --dump-outputs: what the latest step returned (references, no copies)
 
     def barrier(self):
         if DIST["on"]:
@@ -643,6 +732,8 @@ class StepBench:
         hist, longh, fut = self.batches[i % len(self.batches)]
         with torch.no_grad():
             pred, theta, knn, coef = self.model(history_data=hist, long_history_data=longh, future_data=None, batch_seen=i, epoch=None)
+            if self.keep_outputs:
+                self.last = dict(prediction=pred, theta=theta, adj_knn=knn)
             return masked_mae(pred[..., :1] * self.std + self.mean, fut[..., :1] * self.std + self.mean, 0.0)       # base_tsf_runner.py:257-318
 
     def origins(self, i):
@@ -679,6 +770,8 @@ class StepBench:
         return self._staged[i]
 
     def train_step(self, i, epoch=1):
+        if i == self.restore_at:
+            self.state0.restore()
         hist, longh, fut = self.batch(i)
         early = self.prefetch and self.prefetch_early
         if early:                         # the next batch's frozen branch (TSFormer + kNN prior) runs next to the whole of this step
@@ -699,6 +792,8 @@ class StepBench:
         if self.args.torch_optim:
             torch.nn.utils.clip_grad_norm_(self.params, max_norm=3.0)                    # STEP_PEMS04.py:103-105
         self.opt.step()
+        if self.keep_outputs:
+            self.last = dict(prediction=pred.detach(), theta=theta.detach(), adj_knn=knn.detach())
         return loss
 
     def step(self, i):
@@ -716,6 +811,8 @@ class StepBench:
         if DIST["on"]:
             m._reduce_wait_ms = []
         allocs0 = torch.cuda.memory_stats(self.dev).get("num_device_alloc", 0)
+        if self.state0 is not None and self.restore_at is None:
+            self.restore_at = start + warmup + steps - 1
         dt, per_step, loss = timed_loop(self.step, 0, steps, self.barrier, start + warmup)
         allocs = torch.cuda.memory_stats(self.dev).get("num_device_alloc", 0) - allocs0
         if DIST["on"]:
@@ -732,6 +829,14 @@ class StepBench:
         return {"value": B * self.world * steps / dt, "ms_per_step": dt / steps * 1e3, "steps": steps, "warmup": warmup,
                 "p10": float(np.percentile(per_step, 10)), "p50": float(np.percentile(per_step, 50)), "p90": float(np.percentile(per_step, 90)),
                 "host_enqueue_ms_per_step": HOST["enqueue_s"] / steps * 1e3, "device_allocs": int(allocs), "enc_ms": enc_ms, "enc_launches": len(ev), "fallback_units_per_launch": slow / launches, "final_loss": float(loss.detach())}
+
+    def dump(self, path, loss):
+        """--dump-outputs, right after the timed loop: the forward's outputs, the loss (the validation metric with --forward-only) and the gradient
+        norm of the last timed step, which a training run computes from the initial state (InitialState)"""
+        out = dict(self.last, loss=loss)
+        if hasattr(self.opt, "grad_norm") and not self.args.forward_only:
+            out["grad_norm"] = self.opt.grad_norm          # norm of the whole gradient of the last step, as the fused clip + Adam measured it
+        dump_outputs(path, out)
 
     def softmax_units(self):
         P = self.cfg["L"] // 12
@@ -864,6 +969,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="STEP_PEMS04", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the reference config's)")
+    ap.add_argument("--full", action="store_true", help="after the headline loop, also measure everything else the line can carry: the encoder alone, the other "
+                    "schedule and input feed, the random-init figure, the rocprofv3 counter passes, the other configs, the reference's runner loop, "
+                    "the data-parallel exchange figures, the CPU baselines and (--graph) the captured-graph replay; the --no-* options below prune "
+                    "it.  Without it a run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write what the last of them returned -- prediction, theta, "
+                    "adj_knn, loss, grad_norm (pre-training config: reconstruction, label, loss) -- as DIR/<name>.npy, float32 (scalars float64); "
+                    "arrays above 2 M elements as a fixed, seeded sample.  Parameters, running statistics and optimizer are put back to their "
+                    "seeded initial state before that step, so that what it computes is the same every run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-loader-figure", action="store_true", help="skip the second timed loop through the device-resident window loader")
     ap.add_argument("--no-runner-figure", action="store_true", help="skip the child runs that drive the config through the reference's runner loop")
@@ -871,7 +984,10 @@ def main():
     ap.add_argument("--other-configs", default=None, help="comma list of further configs measured after the headline (default: the three "
                     "north-star configs at N=1, none at N>1; '-' = none)")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 counter passes (roofline.traffic falls back to the committed record)")
-    ap.add_argument("--pretrain-steps", type=int, default=300, help="native TSFormer pre-training steps behind the loaded checkpoint (0: random init)")
+    ap.add_argument("--pretrain-steps", type=int, default=300, help="native TSFormer pre-training steps behind the loaded checkpoint (0: random init); at "
+                    "STEP_PEMS04 the checkpoint of 300 steps is a stored run of that recipe (stored_checkpoint), any other is made in this run")
+    ap.add_argument("--fresh-checkpoint", action="store_true", help="make the checkpoint in this run even where a stored one exists (not reproducible "
+                    "from run to run: the pre-training's atomics)")
     ap.add_argument("--prefetch", action="store_true", help="queue the frozen branch (encoder + kNN prior) of the next batch on its own stream "
                     "before this batch's backward (STEP.prefetch).  DEFAULT for the configs of ENC_SPLIT, where the encoder then runs as a "
                     "persistent launch on part of the compute units (--encoder-workgroups) next to the rest of the step")
@@ -908,6 +1024,9 @@ def main():
     args = ap.parse_args()
     if args.pmc_child is not None:
         return pmc_child(args)
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = args.no_pmc = args.no_loader_figure = args.no_runner_figure = True
+        args.other_configs, args.graph = "-", False
     cfg = dict(CONFIGS[args.config])
     if args.batch:
         cfg["B"] = args.batch
@@ -937,7 +1056,7 @@ def main():
     N, Lh, B = cfg["N"], cfg["L"], cfg["B"]
 
     if cfg.get("pretrain"):
-        r = pretrain_run(args, cfg, world, rank, dev, args.warmup, args.steps)
+        r = pretrain_run(args, cfg, world, rank, dev, args.warmup, args.steps, dump=args.dump_outputs)
         if rank == 0:
             print_json_line({"metric": "TSFormer masked pre-training windows/s (config C3)", "value": r["value"], "unit": "windows/s",
                               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
@@ -953,10 +1072,14 @@ def main():
 
     # ---- the checkpoint the model loads: native pre-training, before any timed region
     ckpt, ckpt_info = None, None
-    if args.pretrain_steps > 0:
+    if (args.config, args.pretrain_steps) in [(k, v[1]) for k, v in STORED_CHECKPOINT.items()] and not args.fresh_checkpoint:
+        ckpt, ckpt_info = stored_checkpoint(args.config, cfg, workdir)
+    elif args.pretrain_steps > 0:
         ckpt, ckpt_info = native_checkpoint(args.config.replace("STEP_", ""), cfg, synth_series(cfg["T_all"], N), args.pretrain_steps, dev, workdir)
     bench = StepBench(args.config, cfg, args, world, rank, dev, ckpt)
     res = bench.run(args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        bench.dump(args.dump_outputs, res["final_loss"])
     nxt = args.warmup + args.steps
     extras = not args.no_extras
     enc_alone_ms = bench.encoder_alone_ms(nxt) if (not args.forward_only and extras) else None
@@ -966,7 +1089,7 @@ def main():
                                               ("same step fed by the index-only loader over the device-resident series (step_gather_windows inside the timed region)"
                                                if not bench.use_loader else
                                                "same step cycling eight RESIDENT input batches (the round 1-4 headline): no gather launches, no zero-history windows"))
-    comm = bench.comm_figure() if (DIST["on"] and not args.forward_only) else None
+    comm = bench.comm_figure() if (DIST["on"] and not args.forward_only and args.full) else None
     if args.graph_child:
         # child of graph_replay_figure(): the eager loop above and the replayed loop in ONE process with the runtime's default hardware queues
         gf = bench.graph_figure(max(args.steps, 10))

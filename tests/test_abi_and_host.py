@@ -387,6 +387,22 @@ def test_bench_json_line_is_the_only_line_on_stdout():
         assert out.stderr.count("banner through C stdio") == 2, out.stderr[-500:]
 
 
+def test_bench_dump_outputs_writes_float_arrays_and_a_fixed_sample(tmp_path):
+    """bench.dump_outputs (bench.py --dump-outputs): one <name>.npy per array, float32 whatever the tensor's type (python scalars float64), and an
+    array above bench.DUMP_MAX_ELEMENTS as the SAME sample of its elements on every call -- two builds are compared file by file."""
+    import bench
+    big = torch.arange(bench.DUMP_MAX_ELEMENTS + 12345, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": torch.ones(3, 4, dtype=torch.bfloat16), "big": big, "loss": 1.25})
+    a = {f: np.load(str(tmp_path / "a" / f)) for f in sorted(os.listdir(str(tmp_path / "a")))}
+    assert sorted(a) == ["big.npy", "loss.npy", "small.npy"]
+    assert a["small.npy"].dtype == np.float32 and a["small.npy"].shape == (3, 4) and a["loss.npy"].dtype == np.float64
+    assert a["big.npy"].dtype == np.float32 and a["big.npy"].shape == (bench.DUMP_MAX_ELEMENTS,)
+    assert np.array_equal(a["big.npy"], np.load(str(tmp_path / "b" / "big.npy")))
+    assert (np.diff(a["big.npy"]) >= 0).all() and a["big.npy"][-1] > 0.99 * big.numel()          # spread over the whole array, in order
+    assert bench.DUMP_MAX_ELEMENTS * 4 * 5 <= 64e6                                                # five arrays of a training step: within 64 MB
+
+
 def test_tsformer_flatten_parameters_keeps_the_state_dict_and_shares_one_buffer():
     """TSFormer.flatten_parameters() (host logic, no device needed): every parameter becomes a view into ONE f32 buffer laid out like the
     native backward's flat gradient buffer (parameters in `_pt_names` order, each at a multiple of 4 floats), values, `state_dict` keys and

@@ -76,8 +76,17 @@ def attention_sharpness(sd, series, depth=4):
     return tops
 
 
+def pack(sd, losses, steps, tokens, path):
+    """What the frozen forecasting-mode TSFormer reads of a checkpoint -- patch embedding, the first `tokens` positional rows, the encoder layers,
+    the encoder norm -- as float16 in one .npz below 1 MiB, with the first / last pre-training loss: the stored checkpoint of bench.py."""
+    keep = {"w." + k: (v[:tokens] if k.startswith("positional_encoding.") else v).numpy().astype(np.float16) for k, v in sd.items()
+            if k.startswith(("patch_embedding.", "positional_encoding.", "encoder.", "encoder_norm."))}
+    np.savez(path, steps=np.int64(steps), losses=np.array([losses[0], losses[-1]], dtype=np.float64), **keep)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--pack", default=None, help="also write the encoder side as float16 to this .npz (tests/golden/tsformer_pems04_pretrained.npz)")
     ap.add_argument("--out", default="tsformer_ckpt/TSFormer_PEMS04.pt")
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--batch", type=int, default=6)
@@ -86,9 +95,13 @@ def main():
     import bench
     cfg = bench.CONFIGS[args.config]
     data = bench.synth_series(cfg["T_all"], cfg["N"])
-    sd, losses = pretrain(data, cfg["L"], args.steps, args.batch, log=lambda it, l: print(f"step {it}: loss {l:.3f}", flush=True) if it % 20 == 0 else None)
+    # (--pack: exactly the call bench.native_checkpoint makes -- no per-step read-back of the loss)
+    log = None if args.pack else (lambda it, l: print(f"step {it}: loss {l:.3f}", flush=True) if it % 20 == 0 else None)
+    sd, losses = pretrain(data, cfg["L"], args.steps, args.batch, log=log)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     torch.save({"model_state_dict": sd}, args.out)
+    if args.pack:
+        pack(sd, losses, args.steps, cfg["L"] // 12, args.pack)
     print("saved", args.out, "first/last loss", losses[0], losses[-1])
 
 
