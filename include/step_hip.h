@@ -511,6 +511,23 @@ int step_grad_allreduce(void* comm, float* flat_grad, long n, void* stream);
 int step_grad_allreduce_begin(void* comm, float* flat_grad, long n, void* stream);
 int step_grad_allreduce_join(void* comm, void* stream);
 
+/* ---------------------------------------------------------------- evaluation cache ---------
+ * The reference's recipe runs a whole validation and a whole test pass after every training epoch (CFG.VAL.INTERVAL = CFG.TEST.INTERVAL
+ * = 1, step/STEP_PEMS04.py:126-149; base_tsf_runner.py:276,320) over the same windows, and its TSFormer is frozen (step.py:27-35): of
+ * that branch a forward reads the last patch's hidden state (step.py:64) and the kNN prior graph (discrete_graph_learning.py:164-166)
+ * only.  These two entry points keep both per window in caller-owned HBM and hand them back, so that a later pass replaces
+ * step_gather_windows + step_tsformer_encode + step_knn_graph of a batch by one streaming launch (additive to ABI 10).
+ *  cache_last f32 [capacity][N][96];  cache_bits uint32 [capacity][N][W], W = ceil(N / 32): bit b of word w of row i <-> adj[i][32 w + b] != 0,
+ *             bits of columns >= N are 0 (numpy: packbits(adj != 0, axis=-1, bitorder="little"), padded to whole little-endian words)
+ *  last f32 [B][N][96], adj f32 [B][N][N] (store reads them; load writes them, adj as exactly 0.0f / 1.0f)
+ *  slot int64 [B] on the device: sample b lives in window slot[b] of the cache.  Both calls SKIP a sample whose slot is < 0.
+ * The slots are read on the device and cannot be checked here: THE CALLER GUARANTEES slot[b] < capacity for every sample (a larger
+ * one reads or writes behind the cache).  last and cache_last must be 16-byte aligned.  One launch each. */
+int step_frozen_cache_store(const float* last, const float* adj, int B, int N, const long* slot, long capacity,
+                            float* cache_last, uint32_t* cache_bits, void* stream);
+int step_frozen_cache_load(const float* cache_last, const uint32_t* cache_bits, long capacity, const long* slot, int B, int N,
+                           float* last, float* adj, void* stream);
+
 /* ---------------------------------------------------------------- self test --------------
  * Verifies on the device the MFMA operand/accumulator lane maps this library is built on
  * (cdna_hip_programming.md section 3).  out: int32[8] failure counters, all zero when ok. */

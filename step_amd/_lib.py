@@ -159,6 +159,9 @@ _SIGS = {
     "step_gwnet_forward_phase_dyn": (_i, [_vp, _i, _i, _i, _vp, _vp, _PG, _i, _f, _u64, _f, _vp, _vp, _vp, _i, _vp, _vp]),
     "step_adam_clip_dyn": (_i, [_vp, _vp, _vp, _vp, _l, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "step_loss_scaled_fwd_bwd_dyn": (_i, [_vp, _vp, _l, _l, _f, _f, _vp, _vp, _l, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # evaluation cache of the frozen branch (csrc/eval_cache.hip)
+    "step_frozen_cache_store": (_i, [_vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp]),
+    "step_frozen_cache_load": (_i, [_vp, _vp, _l, _vp, _i, _i, _vp, _vp, _vp]),
 }
 
 _lib = None

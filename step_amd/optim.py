@@ -67,6 +67,8 @@ class FusedAdamClip(torch.optim.Optimizer):
                                    "re-homed by a DDP wrapper): reduce model._flat_grad itself, or step with torch.optim.Adam")
         pg = self.param_groups[0]
         self.step_count += 1
+        if hasattr(self.model, "_drop_eval_g"):
+            self.model._drop_eval_g()          # the kernel writes the parameters through raw pointers (no version bump): STEP's kept eval-mode g is stale
         extra = None
         max_norm = float(self.max_norm or 0.0)
         sh = getattr(getattr(self.model, "discrete_graph_learning", None), "_shard", None)      # (a TSFormer in pre-training mode has no graph learner)

@@ -83,12 +83,14 @@ class DeviceForecastingDataset(Dataset):
     def __len__(self):
         return len(self.index)
 
-    def windows(self, origins, device):
-        """int64 [B] forecast origins -> (future_data [B,H,N,C], history_data [B,H,N,C], LongHistoryRef [B,L,N,C]) on ``device``"""
+    def windows(self, origins, device, host_origins=None):
+        """int64 [B] forecast origins -> (future_data [B,H,N,C], history_data [B,H,N,C], LongHistoryRef [B,L,N,C]) on ``device``.
+        ``host_origins``: the same origins where the caller still holds them on the host (the reference then knows its windows
+        without reading the device: STEP's evaluation cache keys on them)"""
         key = (device.type, device.index)
         if key not in self._loaders:
             self._loaders[key] = DeviceWindowLoader(self.data.to(device), self.seq_len, self.history_len)
-        hist, long_ref, fut = self._loaders[key].batch(origins)
+        hist, long_ref, fut = self._loaders[key].batch(origins, t0_host=None if host_origins is None else host_origins.tolist())
         return fut, hist, long_ref
 
 
@@ -119,7 +121,7 @@ class LookaheadLoader:
         self.staged_batches += 1
         if torch.is_tensor(batch) and batch.dim() == 1 and getattr(self.dataset, "index_only", False):
             origins = batch if batch.is_pinned() or batch.is_cuda else batch.pin_memory()
-            return self.dataset.windows(origins.to(dev, non_blocking=True), dev)
+            return self.dataset.windows(origins.to(dev, non_blocking=True), dev, host_origins=None if batch.is_cuda else batch)
         if dev.type != "cuda":
             return batch
         if self._copy_stream is None:
@@ -179,10 +181,15 @@ class _Deferred:
         return self
 
 
-def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, encoder_workgroups=None, native_metrics=True):
+def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, encoder_workgroups=None, native_metrics=True,
+                  eval_cache_bytes=0):
     """-> subclass of ``base`` (the reference's ``STEPRunner``, or any ``BaseTimeSeriesForecastingRunner``) for ``CFG.RUNNER``.
     ``encoder_workgroups``: compute units of the persistent encoder launch next to the step (None: 160 at 307 nodes / 336 tokens, the
-    measured optimum of config C2; 0: one workgroup per sequence) -- only used while batches are prefetched."""
+    measured optimum of config C2; 0: one workgroup per sequence) -- only used while batches are prefetched.
+    ``eval_cache_bytes``: HBM budget of ``STEP.eval_cache_bytes`` for the validation and test passes (0, the default: off).  With
+    ``DeviceForecastingDataset`` the batches carry their origins on the host, and the second and every later ``validate()`` /
+    ``test()`` pass over the same windows loads the frozen TSFormer branch instead of computing it (about 130 KB per window at
+    PEMS04)."""
 
     class NativeRunner(base):
         native_hooks = True
@@ -208,10 +215,17 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                 model.prefetch_knn_stream = int(n) > 0          # (the look-ahead loader announces at the start of the step: bench.py's policy)
             return loader
 
+        def _enable_eval_cache(self):
+            model = _unwrap(self.model)
+            if eval_cache_bytes > 0 and isinstance(model, STEP):
+                model.eval_cache_bytes = int(eval_cache_bytes)
+
         def build_val_data_loader(self, cfg):
+            self._enable_eval_cache()
             return self._lookahead(super().build_val_data_loader(cfg), False)
 
         def build_test_data_loader(self, cfg):
+            self._enable_eval_cache()
             return self._lookahead(super().build_test_data_loader(cfg), False)
 
         # ---------------------------------------------------------------- feature selection without a host-device synchronisation

@@ -124,6 +124,7 @@ class DiscreteGraphLearning(nn.Module):
             dist.broadcast(buf, dist.get_global_rank(process_group, r) if process_group is not None else r, group=process_group)
             full[:, :, a:b].copy_(buf)
         self._slice_dirty = False
+        self._gather_count = getattr(self, "_gather_count", 0) + 1      # fc.weight.data was written in place (no version bump): STEP's kept eval-mode g is stale
 
     def refresh_fc_weight_slice(self):
         """after loading a (full) state_dict into a sharded module: re-cut this rank's slice from ``fc.weight``"""

@@ -17,6 +17,7 @@ from .. import _lib
 from .tsformer import TSFormer
 from .graphwavenet import GraphWaveNet, fill_gwnet_struct
 from .discrete_graph_learning import DiscreteGraphLearning, fill_dgl_struct
+from . import eval_cache as _ec
 
 TEMPERATURE = 0.5        # discrete_graph_learning.py:157
 BN_MOMENTUM = 0.1
@@ -34,10 +35,14 @@ class LongHistoryRef:
     (step/step_runner/step_runner.py:58-63): ``.to(device)`` / ``.cuda()`` (already there: itself), ``.shape``, and the feature
     selection ``data[:, :, :, forward_features]`` (a reference to the same windows exposing those channels)."""
 
-    def __init__(self, data, t0, length, channels=None):
+    def __init__(self, data, t0, length, channels=None, t0_host=None):
         assert data.is_cuda and data.dtype == torch.float32 and data.dim() == 3 and data.is_contiguous()
         assert t0.is_cuda and t0.dtype == torch.int64 and t0.dim() == 1
         self.data, self.t0, self.length = data, t0, int(length)
+        # the same origins as host integers when the loader had them there (None: device only) -- the identity of the batch's windows
+        # for STEP's evaluation cache, which must not read `t0` back
+        self.t0_host = None if t0_host is None else tuple(int(t) for t in t0_host)
+        assert self.t0_host is None or len(self.t0_host) == t0.shape[0]
         self.channels = list(range(data.shape[2])) if channels is None else [int(c) for c in channels]      # data channels this reference exposes, in order
 
     @property
@@ -64,7 +69,7 @@ class LongHistoryRef:
                 sel = list(range(len(self.channels)))[sel]
             elif torch.is_tensor(sel):
                 sel = sel.tolist()
-            return LongHistoryRef(self.data, self.t0, self.length, [self.channels[int(c)] for c in sel])
+            return LongHistoryRef(self.data, self.t0, self.length, [self.channels[int(c)] for c in sel], t0_host=self.t0_host)
         raise IndexError("LongHistoryRef supports the runner's feature selection only: ref[:, :, :, features]")
 
 
@@ -77,14 +82,18 @@ class DeviceWindowLoader:
         assert self.data.is_cuda
         self.long_len, self.horizon = int(long_len), int(horizon)
 
-    def batch(self, t0):
+    def batch(self, t0, t0_host=None):
+        """``t0``: forecast origins (list, numpy array, CPU or device tensor).  ``t0_host``: the same origins on the host when ``t0``
+        is already a device tensor (a loader that staged them itself); origins handed in on the host are kept as they are."""
+        if t0_host is None and not (torch.is_tensor(t0) and t0.is_cuda):
+            t0_host = t0.tolist() if hasattr(t0, "tolist") else list(t0)
         t0 = torch.as_tensor(t0, dtype=torch.int64, device=self.data.device).contiguous()
         B, (T, N, C), H = t0.shape[0], self.data.shape, self.horizon
         hist = torch.empty(B, H, N, C, device=self.data.device)
         fut = torch.empty(B, H, N, C, device=self.data.device)
         _lib.call("step_gather_windows", _lib.ptr(self.data), T, N, C, 0, _lib.ptr(t0), B, 0, H, None, _lib.ptr(hist), _lib.ptr(fut),
                   _lib.stream())
-        return hist, LongHistoryRef(self.data, t0, self.long_len), fut
+        return hist, LongHistoryRef(self.data, t0, self.long_len, t0_host=t0_host), fut
 
 
 class _StepFunction(torch.autograd.Function):
@@ -100,6 +109,10 @@ class _StepFunction(torch.autograd.Function):
         st = L.stream()
         hist = hist.contiguous().float()
         frozen = model._take_prefetched(long_hist)      # the frozen branch of this batch, if STEP.prefetch() already queued it
+        # evaluation cache (STEP.eval_cache_bytes; STEP.forward decided whether it is active for this call): `ec` is the batch's plan,
+        # None for a batch without host origins -- which runs as if the cache were off
+        ec_on, model._ec_on = model._ec_on, False
+        ec = model._eval_cache_plan(long_hist, N, Lh // 12, dev) if ec_on else None
         # Everything up to the GraphWaveNet head is independent of the (frozen) TSFormer: the DGL's global feature, the edge
         # logits, the Gumbel sample and the 8 WaveNet layers only need the train series, the short history and the weights.
         # They are queued on a second stream next to the encoder: its workgroups keep the compute units busy while that chain of
@@ -122,9 +135,17 @@ class _StepFunction(torch.autograd.Function):
         Ttr = dgl.train_length if sh is None else sh["Ts"]
         series_nt = dgl._series_nt if sh is None else dgl._series_slice
         drop = be.dropout if training else 0.0
-        gsaved = _f32(L.lib().step_dgl_global_saved_floats(N, Ttr), dev)
-        gwork = _f32(L.lib().step_dgl_global_work_floats(N, Ttr, 0), dev)
-        g = _f32(N * 100, dev).view(N, 100)
+        # eval-invariant global feature: with the cache active g is kept from the first forward (it reads the train series and the
+        # learner's weights only, BatchNorm on running statistics) and step_dgl_global_forward is skipped while nothing it reads changed
+        g_key = model._eval_g_key(bf, N, Ttr) if ec_on else None
+        g = model._eval_g_lookup(g_key) if g_key is not None else None
+        g_kept = g is not None
+        if g_kept:
+            gsaved = gwork = None          # (only a backward reads gsaved; none can follow a forward without gradients)
+        else:
+            gsaved = _f32(L.lib().step_dgl_global_saved_floats(N, Ttr), dev)
+            gwork = _f32(L.lib().step_dgl_global_work_floats(N, Ttr, 0), dev)
+            g = _f32(N * 100, dev).view(N, 100)
         esaved = _f32(L.lib().step_dgl_edges_saved_floats(B, N), dev)
         # theta is one of the tensors the edge backward reads from `esaved`: returned as a view of it, written once (a separate output
         # tensor cost a 3 MB device copy on the second stream's chain, 217 us next to the encoder)
@@ -157,7 +178,9 @@ class _StepFunction(torch.autograd.Function):
                 prep_done.record(prep)
 
         def graph_and_layers(sst):
-            if sh is None:
+            if g_kept:
+                pass
+            elif sh is None:
                 L.call("step_dgl_global_forward", L.ptr(series_nt), N, Ttr, ctypes.byref(dstruct), int(training), BN_MOMENTUM,
                        L.ptr(gsaved), L.ptr(gwork), L.ptr(g), sst)
             else:
@@ -185,6 +208,8 @@ class _StepFunction(torch.autograd.Function):
                     torch._foreach_add_([m.num_batches_tracked for m in (dgl.bn1, dgl.bn2, dgl.bn3, *list(be.bn)[:8 if model.track_dead_bn7 else 7])], 1)
 
         # ---- TSFormer (frozen) and the kNN prior graph (no grad): on the main stream, or already in flight on the prefetch stream
+        if frozen is None and ec is not None and ec["hit"]:
+            frozen = model._eval_cache_load(ec, B, N, dev)          # every window of the batch is stored: one launch, no encoder, no kNN
         if frozen is None:
             # (the kNN prior is only needed by the loss; running its Gram product and top-k selection on a third stream next to the
             #  GraphWaveNet head was measured: 4.72 vs 4.69 ms, the Gram product takes the compute units from the head's small kernels --
@@ -221,6 +246,10 @@ class _StepFunction(torch.autograd.Function):
                float(drop), seed_gw, BN_MOMENTUM, L.ptr(wsaved), L.ptr(wwork), L.ptr(pred), 4, st)
         if frozen.get("knn_done") is not None:
             main.wait_event(frozen["knn_done"])          # adj_knn / sim are handed to the caller on the current stream
+        if ec is not None:
+            model._eval_cache_store(ec, frozen, B, N, dev)          # the windows not stored yet (nothing for a batch served from the cache)
+        if g_key is not None and not g_kept:
+            model._eval_g = (g_key, g)
         ctx.model = model
         ctx.dims = (B, N, Cin, Ttr, float(drop))
         ctx.held = (hist, enc["last"], g, gsaved, esaved, wsaved)
@@ -340,6 +369,7 @@ class _StepFunction(torch.autograd.Function):
         del wwork, ework
         model._flat_grad = flat
         model._backward_count = getattr(model, "_backward_count", 0) + 1
+        model._drop_eval_g()          # the optimizer is about to write the learner's weights through raw pointers
         ctx.held = None
         del views, gw_grads, dg_grads
         if model.flat_gradients_only:
@@ -451,6 +481,18 @@ class STEP(nn.Module):
         self._reduce_wait_ms = None         # bench.py: list that collect_reduce_waits() fills
         self._reduce_events = []
         self._small_events = []             # (start, end, bytes) of the time-sliced graph learner's blocking sums (bench.py)
+        # Evaluation cache (off by default).  eval_cache_bytes > 0: HBM budget for the frozen branch of evaluation windows -- per window
+        # the last patch's hidden state [N, 96] f32 and the kNN prior as one bit per edge (130 KB at PEMS04).  In eval mode without
+        # gradients, a batch of a LongHistoryRef that carries host origins (t0_host) whose windows are all stored launches no encoder, no
+        # Gram product and no top-k (one step_frozen_cache_load instead); other batches run as always and are stored afterwards, up
+        # to the budget (no eviction).  The graph learner's global feature g is kept across such forwards as well.  See _eval_cache_plan.
+        self.eval_cache_bytes = 0
+        self._eval_cache_chunk_windows = 256          # storage grows by this many windows at a time (read when the storage is created)
+        self.eval_cache_stats = _ec.new_stats()
+        self._eval_cache = None             # eval_cache.FrozenBranchCache
+        self._eval_cache_alloc = None       # tests: allocator of the storage chunks (None: device tensors)
+        self._eval_g = None                 # (key, g [N, 100]) of the last eval-mode global forward, see _eval_g_key
+        self._ec_on = False                 # forward() -> _StepFunction.forward: the cache is active for this call
 
     def load_pre_trained_model(self):
         """step.py:27-35: load {"model_state_dict": ...} and freeze."""
@@ -459,6 +501,8 @@ class STEP(nn.Module):
             self.tsformer.load_state_dict(ckpt["model_state_dict"])
         for p in self.tsformer.parameters():
             p.requires_grad = False
+        if "_eval_cache" in self.__dict__:
+            self._invalidate_eval_cache()
 
     # ------------------------------------------------------------------ helpers
     def _side_stream(self, dev, name="side"):
@@ -493,7 +537,10 @@ class STEP(nn.Module):
             long_hist = long_hist.contiguous().float()
             L.call("step_pack_long_history", L.ptr(long_hist), B, Lh, N, long_hist.shape[3], int(channel), L.ptr(series), st)
         P = Lh // 12
+        tie = self._eval_cache_tie(N, P) if (self.eval_cache_bytes > 0 and not self.training) else None          # (nothing is stored in training mode)
         enc = self.tsformer.encode_series(series)
+        if tie is not None and self._eval_cache_tie(N, P) != tie:
+            tie = None          # the range guard re-ran this launch on bfloat16 (or repacked): not a branch to keep
         sim = _f32(B * N * N, dev).view(B, N, N)
         adj_knn = _f32(B * N * N, dev).view(B, N, N)
         kwork = torch.empty(L.lib().step_knn_workspace_bytes(B, N, P * 96), dtype=torch.uint8, device=dev)
@@ -512,7 +559,7 @@ class STEP(nn.Module):
         else:
             L.call("step_knn_graph", L.ptr(enc["hidden_bf16"]), L.ptr(enc["sqnorm"]), B, N, P * 96, self.discrete_graph_learning.k * N,
                    L.ptr(sim), L.ptr(adj_knn), L.ptr(kwork), kwork.numel(), st)
-        return {"enc": enc, "sim": sim, "adj_knn": adj_knn, "held": (series, kwork, long_hist), "done": None, "knn_done": knn_done}
+        return {"enc": enc, "sim": sim, "adj_knn": adj_knn, "held": (series, kwork, long_hist), "done": None, "knn_done": knn_done, "tie": tie}
 
     @staticmethod
     def _batch_key(long_hist, channel=0):
@@ -548,7 +595,11 @@ class STEP(nn.Module):
             if not long_history_data.is_cuda:
                 raise RuntimeError("step_amd.STEP runs only on an AMD GPU: libstep_hip has no CPU fallback")
             dev = long_history_data.device
-        B, _, N, _ = long_history_data.shape
+        B, Lh, N, _ = long_history_data.shape
+        if self._eval_cache is not None and self._eval_cache_active():
+            ec = self._eval_cache_plan(long_history_data, N, Lh // 12, dev, channel)
+            if ec is not None and ec["hit"]:
+                return          # every window of the batch is stored: forward() will load them, nothing to queue
         main = torch.cuda.current_stream()
         ps = self._prefetch_stream(dev)
         ready = torch.cuda.Event()
@@ -624,6 +675,115 @@ class STEP(nn.Module):
         # behind the queued branches -- which stay queued for the batches they were announced for
         for rec in q:
             self._wait_record(main, rec)
+        return None
+
+    # ------------------------------------------------------------------ evaluation cache (eval_cache_bytes)
+    def _eval_cache_active(self):
+        """The cache serves and stores only where a forward is a pure function of (window, weights): eval mode (no dropout, BatchNorm
+        on running statistics), no gradient to be taken (a backward reads buffers a cached forward does not produce), no stream
+        capture (the plan is host state), and a graph learner that is not cut into time slices (its evaluation rules stay as they
+        are)."""
+        if self.eval_cache_bytes <= 0 or self.training or self.discrete_graph_learning._shard is not None:
+            return False
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self._trainable_list()):
+            return False
+        return not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing())
+
+    def _eval_cache_tie(self, N, P):
+        """what a stored window depends on besides the window itself: any TSFormer parameter's address or version and the requested
+        operand type (_pack_key), the operand type in use and the range guard's switches, the number of patches, k, N"""
+        ts = self.tsformer
+        return (ts._pack_key(int(P)), ts.encoder_operand_in_use, ts.range_fallbacks, int(P), int(self.discrete_graph_learning.k), int(N))
+
+    def _invalidate_eval_cache(self):
+        """drop the stored windows and the kept g (the weights, the operand type or the module's storage changed)"""
+        if self._eval_cache is not None and self._eval_cache.slots:
+            self.eval_cache_stats["invalidations"] += 1
+        self._eval_cache = None
+        self._eval_g = None
+
+    def clear_eval_cache(self):
+        """free everything the evaluation cache holds (the counters of eval_cache_stats stay)"""
+        self._eval_cache = None
+        self._eval_g = None
+
+    def _drop_eval_g(self):
+        self._eval_g = None
+
+    def _eval_cache_plan(self, long_hist, N, P, dev=None, channel=0):
+        """-> {"cache", "keys", "hit", ...} for a batch with host origins, None otherwise.  Compares the cache's tie first and drops a
+        stale cache.  No device call."""
+        keys = _ec.window_keys(long_hist, channel) if hasattr(long_hist, "t0_host") else None
+        if keys is None:
+            return None
+        self.tsformer.range_poll_check()          # a landed poll of the float16 range flag switches the operand type: part of the tie
+        tie = self._eval_cache_tie(N, P)
+        c = self._eval_cache
+        if c is not None and (c.tie != tie or c.budget != int(self.eval_cache_bytes)):
+            self._invalidate_eval_cache()
+            c = None
+        if c is None:
+            alloc = self._eval_cache_alloc or _ec._device_alloc(dev)
+            c = self._eval_cache = _ec.FrozenBranchCache(self.eval_cache_bytes, N, tie, alloc, self._eval_cache_chunk_windows)
+        return {"cache": c, "keys": keys, "hit": c.is_hit(keys), "series": long_hist.data, "served": False}
+
+    @staticmethod
+    def _slot_tensor(slots, dev):
+        """slot indices for the device: a small pinned tensor, copied without making the host wait"""
+        return torch.tensor(slots, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+
+    def _eval_cache_load(self, ec, B, N, dev):
+        """the `frozen` record of a batch whose windows are all stored: fresh last [B*N, 96] and adj_knn [B, N, N] filled by
+        step_frozen_cache_load (one launch; one per storage chunk for a batch that straddles chunks); nothing else of the branch exists"""
+        L = _lib
+        c = ec["cache"]
+        last = _f32(B * N * 96, dev).view(B * N, 96)
+        adj_knn = _f32(B * N * N, dev).view(B, N, N)
+        for ci, local in c.plan(c.lookup(ec["keys"])):
+            cl, cb, cap = c.chunks[ci]
+            L.call("step_frozen_cache_load", L.ptr(cl), L.ptr(cb), cap, L.ptr(self._slot_tensor(local, dev)), B, N, L.ptr(last), L.ptr(adj_knn),
+                   L.stream())
+        self.tsformer._seed_counter += 1          # as the skipped encoder launch would have: later dropout seeds do not move
+        ec["served"] = True
+        self.eval_cache_stats["window_hits"] += B
+        return {"enc": {"hidden_bf16": None, "hidden_f32": None, "last": last, "sqnorm": None}, "sim": None, "adj_knn": adj_knn,
+                "held": (), "done": None, "knn_done": None}
+
+    def _eval_cache_store(self, ec, frozen, B, N, dev):
+        """after a computed batch: one step_frozen_cache_store of its windows that are not stored yet, on the current stream behind
+        the branch.  Nothing is stored from a launch the float16 range guard has not cleared, from one it re-ran on bfloat16, or
+        from a branch computed under another tie (announced before the weights changed)."""
+        if ec["served"]:
+            return
+        c, ts = ec["cache"], self.tsformer
+        self.eval_cache_stats["window_misses"] += sum(1 for k in ec["keys"] if k not in c.slots)          # computed because they were not stored
+        if frozen.get("tie") != c.tie or not ts.range_cleared() or self._eval_cache_tie(N, c.tie[3]) != c.tie:
+            return
+        slots, stored, refused = c.assign(ec["keys"], ec["series"])
+        self.eval_cache_stats["windows_stored"] += stored
+        self.eval_cache_stats["windows_refused"] += refused
+        L = _lib
+        for ci, local in c.plan(slots):
+            cl, cb, cap = c.chunks[ci]
+            L.call("step_frozen_cache_store", L.ptr(frozen["enc"]["last"]), L.ptr(frozen["adj_knn"]), B, N, L.ptr(self._slot_tensor(local, dev)),
+                   cap, L.ptr(cl), L.ptr(cb), L.stream())
+
+    def _eval_g_key(self, bf, N, Ttr):
+        """identity of everything step_dgl_global_forward reads in eval mode: the series, the precision mode, address and version of the
+        learner's tensors.  Kernels that write parameters through raw pointers do not bump versions: those call _drop_eval_g()."""
+        if self._precision_override is not None:
+            return None
+        dgl = self.discrete_graph_learning
+        sr = dgl._series_nt
+        return (int(bf), int(N), int(Ttr), sr.data_ptr(), sr._version, getattr(dgl, "_gather_count", 0),
+                tuple((v.data_ptr(), v._version) for v in dgl.native_tensors(full=True).values()))
+
+    def _eval_g_lookup(self, key):
+        kept = self._eval_g
+        if kept is not None and kept[0] == key:
+            self.eval_cache_stats["g_reuses"] += 1
+            return kept[1]
+        self._eval_g = None
         return None
 
     def _prefetch_stream(self, dev):
@@ -745,6 +905,7 @@ class STEP(nn.Module):
         the CPU tests run over gloo); "auto" (default) -- "rccl" when the group's backend is nccl (= RCCL) and the parameters live on a
         GPU, else "torch"."""
         import torch.distributed as dist
+        self._eval_g = None                 # the parameter broadcast below writes the learner's weights
         self._process_group = process_group if process_group is not None else dist.group.WORLD
         self._min_world = 0 if single_rank_collectives else 1
         if self._comm is not None:
@@ -908,11 +1069,14 @@ class STEP(nn.Module):
     def train(self, mode=True):
         if bool(mode) != self.training and self._prefetched:
             self.cancel_prefetch()          # a branch queued for the other mode will not be consumed (see _take_prefetched)
+        if mode:
+            self._eval_g = None             # training is about to change the learner's weights (the stored windows only depend on the frozen TSFormer)
         return super().train(mode)
 
     def _apply(self, fn, recurse=True):
         self._zg_params = None
         self._struct_cache, self._bwd_cache, self._trainable_cache = {}, None, None
+        self._invalidate_eval_cache()
         out = super()._apply(fn, recurse)
         flat = self._flat_param
         if flat is not None:
@@ -926,6 +1090,7 @@ class STEP(nn.Module):
     def load_state_dict(self, *a, **kw):
         self._zg_params = None
         self._struct_cache, self._bwd_cache, self._trainable_cache = {}, None, None
+        self._invalidate_eval_cache()
         return super().load_state_dict(*a, **kw)
 
     # ------------------------------------------------------------------ forward
@@ -940,6 +1105,7 @@ class STEP(nn.Module):
         else:
             u = None
         params = self._trainable_list()
+        self._ec_on = self.eval_cache_bytes > 0 and self._eval_cache_active()
         pred, theta, adj_knn = _StepFunction.apply(self, history_data, long_history_data, u, *params)
         if epoch is not None:
             gsl_coefficient = 1 / (int(epoch / 6) + 1)

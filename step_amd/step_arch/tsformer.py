@@ -624,6 +624,19 @@ class TSFormer(nn.Module):
         warnings.warn(f"step_amd.TSFormer: float16 operand overflow in the fused encoder ({where}): non-finite hidden states; "
                       "the encoder now runs bfloat16 operand fragments (exponent range of fp32)")
 
+    def range_poll_check(self):
+        """act on a periodic poll of the range flag that has landed (every encoder launch starts with this; STEP's evaluation cache
+        asks before it serves stored windows, which launch nothing)"""
+        guard = self.range_guard and self.encoder_operand == "f16"
+        if guard and not self._range_forced_bf16 and self._range_poll_result() and not torch.cuda.is_current_stream_capturing():
+            self._range_overflowed("found by the periodic poll; batches since the previous poll carried NaN")
+
+    def range_cleared(self):
+        """True when the float16 range guard has nothing open on the current weights: it is off (or the operands are bfloat16), or the
+        first `range_check_launches` launches -- each looked at right away -- are behind it"""
+        guard = self.range_guard and self.encoder_operand == "f16" and not self._range_forced_bf16
+        return (not guard) or self._range_checked >= self.range_check_launches
+
     def dropout_pool(self, device, drop, seed, L):
         """The keep-mask pool for this launch: (int64 tensor viewed as 64-bit words, number of words).  ``_pool_override``
         (tests) supplies the bits instead of the Philox fill, so a test can reproduce every mask on the host."""
@@ -655,8 +668,7 @@ class TSFormer(nn.Module):
             raise AssertionError("long history length must be a multiple of the patch size")   # patch.py:41
         P = L // self.patch_size
         guard = self.range_guard and self.encoder_operand == "f16"
-        if guard and not self._range_forced_bf16 and self._range_poll_result() and not torch.cuda.is_current_stream_capturing():
-            self._range_overflowed("found by the periodic poll; batches since the previous poll carried NaN")
+        self.range_poll_check()
         pk = self.packed_weights(P, series.device)
         out = {"hidden_bf16": torch.empty(S, P, 96, device=series.device, dtype=torch.bfloat16) if want_bf16 else None,
                "hidden_f32": torch.empty(S, P, 96, device=series.device) if want_f32 else None,
