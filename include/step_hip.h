@@ -528,6 +528,27 @@ int step_frozen_cache_store(const float* last, const float* adj, int B, int N, c
 int step_frozen_cache_load(const float* cache_last, const uint32_t* cache_bits, long capacity, const long* slot, int B, int N,
                            float* last, float* adj, void* stream);
 
+/* ---------------------------------------------------------------- evaluation metrics -------
+ * The reference's test pass keeps every prediction of the pass, rescales the concatenation and slices it per horizon for its three
+ * masked metrics (basicts/runners/base_tsf_runner.py:277-318; its validation pass averages the per-batch values, :257-273).  These
+ * entry points accumulate the same numbers on the device, batch by batch, and hand them back in one array (additive to ABI 10).
+ *  pred, real   f32 views [B, H, N] given by ELEMENT strides (a prediction [B, H, N, 1]; a label that is one channel of [B, H, N, C]);
+ *               both normalised: the metrics are taken on x * scale + shift, a rounded multiply then a rounded add, like
+ *               re_standard_transform (basicts/data/transform.py) in front of the reference's metrics
+ *  acc          f64 [the size the _acc_doubles entry returns for H], ZEROED BY THE CALLER once per pass; _accumulate only adds to it,
+ *               _finish leaves it as it is.  Calls on one accumulator must be ordered by their stream.
+ *  semantics    basicts/metrics/{mae,rmse,mape}.py applied to the concatenation of everything accumulated:
+ *               m = !(|y - null_val| <= 5e-5), or !isnan(y) for a NaN null_val (a NaN label next to a finite null_val counts);
+ *               MAE = S_abs / cnt, RMSE = sqrt(S_sq / cnt), cnt = sum m; a NaN term adds 0 and still counts, an infinite one stays;
+ *               MAPE: y0 = |y| < 1e-4 ? 0 : y, m0 = !(|y0| <= 5e-5), sum |(|p - y0|) / y0| / sum m0; a count of 0 gives 0
+ *  out          f64 [(H + 2) * 3] = {MAE, RMSE, MAPE} of horizon h at 3 h; of all horizons at 3 H; at 3 (H + 1) the equal-weight mean
+ *               over the _accumulate calls of each call's own overall metrics (what the validation meters average)
+ * H <= 64, B * N < 2^31.  One launch per call. */
+long step_eval_metrics_acc_doubles(int H);          /* 0 for H < 1 or H > 64; pure host function */
+int step_eval_metrics_accumulate(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh, long r_sn,
+                                 int B, int H, int N, float scale, float shift, float null_val, double* acc, void* stream);
+int step_eval_metrics_finish(const double* acc, int H, double* out, void* stream);
+
 /* ---------------------------------------------------------------- self test --------------
  * Verifies on the device the MFMA operand/accumulator lane maps this library is built on
  * (cdna_hip_programming.md section 3).  out: int32[8] failure counters, all zero when ok. */

@@ -13,7 +13,10 @@ def __getattr__(name):
     if name in ("LongHistoryRef", "DeviceWindowLoader"):          # device-resident dataset, index-only loader
         from .step_arch import step
         return getattr(step, name)
-    if name == "GraphedTrainStep":          # one captured hipGraph per training step
+    if name in ("EvalMetrics", "EvalResult"):          # per-horizon metrics of a validation / test pass, accumulated on the device
+        from . import evaluate
+        return getattr(evaluate, name)
+    if name == "GraphedTrainStep":       # one captured hipGraph per training step
         from .graphed import GraphedTrainStep
         return GraphedTrainStep
     raise AttributeError(name)

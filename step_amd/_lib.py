@@ -162,6 +162,10 @@ _SIGS = {
     # evaluation cache of the frozen branch (csrc/eval_cache.hip)
     "step_frozen_cache_store": (_i, [_vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp]),
     "step_frozen_cache_load": (_i, [_vp, _vp, _l, _vp, _i, _i, _vp, _vp, _vp]),
+    # per-horizon evaluation metrics of a whole pass (csrc/eval_metrics.hip)
+    "step_eval_metrics_acc_doubles": (_l, [_i]),
+    "step_eval_metrics_accumulate": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _f, _f, _f, _vp, _vp]),
+    "step_eval_metrics_finish": (_i, [_vp, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -87,11 +87,15 @@ class DeviceForecastingDataset(Dataset):
         """int64 [B] forecast origins -> (future_data [B,H,N,C], history_data [B,H,N,C], LongHistoryRef [B,L,N,C]) on ``device``.
         ``host_origins``: the same origins where the caller still holds them on the host (the reference then knows its windows
         without reading the device: STEP's evaluation cache keys on them)"""
+        hist, long_ref, fut = self.device_loader(device).batch(origins, t0_host=None if host_origins is None else host_origins.tolist())
+        return fut, hist, long_ref
+
+    def device_loader(self, device):
+        """the dataset's ``DeviceWindowLoader`` on ``device``: the series is moved there once"""
         key = (device.type, device.index)
         if key not in self._loaders:
             self._loaders[key] = DeviceWindowLoader(self.data.to(device), self.seq_len, self.history_len)
-        hist, long_ref, fut = self._loaders[key].batch(origins, t0_host=None if host_origins is None else host_origins.tolist())
-        return fut, hist, long_ref
+        return self._loaders[key]
 
 
 class LookaheadLoader:

@@ -1112,3 +1112,12 @@ class STEP(nn.Module):
         else:
             gsl_coefficient = 0
         return pred, theta, adj_knn, gsl_coefficient
+
+    # ------------------------------------------------------------------ validation / test pass
+    def evaluate(self, loader, origins=None, scaler=None, null_val=0.0, batch_size=None, target_channel=0, horizons=None,
+                 return_predictions=False):
+        """One validation / test pass over a device-resident series with the reference's masked MAE / RMSE / MAPE per horizon, overall
+        and per batch accumulated on the device and read back once: ``step_amd.evaluate.evaluate_pass`` (documented there)."""
+        from ..evaluate import evaluate_pass
+        return evaluate_pass(self, loader, origins, scaler=scaler, null_val=null_val, batch_size=batch_size, target_channel=target_channel,
+                             horizons=horizons, return_predictions=return_predictions)
