@@ -549,6 +549,30 @@ int step_eval_metrics_accumulate(const float* pred, long p_sb, long p_sh, long p
                                  int B, int H, int N, float scale, float shift, float null_val, double* acc, void* stream);
 int step_eval_metrics_finish(const double* acc, int H, double* out, void* stream);
 
+/* ---------------------------------------------------------------- training tail -----------
+ * The tail of one training iteration in two launches: the loss of step/step_loss/step_loss.py:5-16 on the first k horizon steps of the
+ * RESCALED prediction and label (curriculum learning, basicts/runners/base_tsf_runner.py:170-190, 243-246), both of its gradients, and
+ * the three training meters of base_tsf_runner.py:252-254 (basicts/metrics/{mae,rmse,mape}.py) on the same slice -- instead of the two
+ * re_standard_transform calls (:240-241), the two [:, :k] slices, the loss, the three metric functions and their autograd nodes.
+ *  pred, real   f32, NORMALISED; element (b, h, n) at b * sb + h * sh + n * sn floats (the label is read in place as one channel of
+ *               [B, H, N, C]); the terms are taken on x * scale + shift, rounded twice as torch does
+ *  k            1 <= k <= H <= 64: horizons 0 .. k - 1 are included
+ *  theta, prior f32 [n_adj] contiguous; coef the graph term's weight
+ *  work         f64 [step_train_tail_work_doubles()], zero before the FIRST call, then left to the calls of ONE stream: two halves of
+ *               six sums {S_abs, S_sq, cnt, S_ape, cnt0, S_bce} used by alternate calls (a call's second launch clears the half of the
+ *               next call: no memset is queued) and the call index
+ *  loss         f32 [1] = S_abs / cnt + coef * S_bce / n_adj, m = !(|y - null_val| <= 5e-5) (null_val finite); cnt == 0 leaves the
+ *               graph term
+ *  metrics      f32 [3] = MAE, RMSE, MAPE with the definitions of step_eval_metrics_accumulate (a NaN term adds 0 and still counts)
+ *  dpred        f32 [B * H * N] contiguous, ALL of it written: sign(p - y) * scale / cnt at included, unmasked elements; exactly 0 at
+ *               excluded horizons, masked labels and NaN differences
+ *  dtheta       f32 [n_adj] = coef / n_adj * (theta - prior) / max(theta (1 - theta), 1e-12)
+ * B * H * N < 2^31. */
+long step_train_tail_work_doubles(void);          /* pure host function */
+int step_train_tail(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh, long r_sn, int B, int H,
+                    int N, int k, float scale, float shift, float null_val, const float* theta, const float* prior, long n_adj, float coef,
+                    double* work, float* loss, float* metrics, float* dpred, float* dtheta, void* stream);
+
 /* ---------------------------------------------------------------- self test --------------
  * Verifies on the device the MFMA operand/accumulator lane maps this library is built on
  * (cdna_hip_programming.md section 3).  out: int32[8] failure counters, all zero when ok. */

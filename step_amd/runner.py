@@ -30,6 +30,8 @@ implementation and only changes WHERE the data lives and WHEN the host reads num
 
 Nothing here imports the reference or easytorch: the base class is handed in by the config file, which lives in the reference tree.
 """
+import math
+import numbers
 import os
 import pickle
 
@@ -186,14 +188,19 @@ class _Deferred:
 
 
 def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, encoder_workgroups=None, native_metrics=True,
-                  eval_cache_bytes=0):
+                  eval_cache_bytes=0, native_tail=False):
     """-> subclass of ``base`` (the reference's ``STEPRunner``, or any ``BaseTimeSeriesForecastingRunner``) for ``CFG.RUNNER``.
     ``encoder_workgroups``: compute units of the persistent encoder launch next to the step (None: 160 at 307 nodes / 336 tokens, the
     measured optimum of config C2; 0: one workgroup per sequence) -- only used while batches are prefetched.
     ``eval_cache_bytes``: HBM budget of ``STEP.eval_cache_bytes`` for the validation and test passes (0, the default: off).  With
     ``DeviceForecastingDataset`` the batches carry their origins on the host, and the second and every later ``validate()`` /
     ``test()`` pass over the same windows loads the frozen TSFormer branch instead of computing it (about 130 KB per window at
-    PEMS04)."""
+    PEMS04).
+    ``native_tail``: take the loss, its gradients and the three training meters of an iteration from ONE ``step_loss.train_tail`` call
+    on the model's normalised prediction and the batch's target view -- no rescale, no ``[:, :cl_length]`` slice, no copy -- also under
+    curriculum learning (``CFG.TRAIN.CL``).  Needs a ``STEP`` module on a GPU, the ``re_standard_transform`` scaler with scalar
+    mean / std, ``step_loss`` / ``step_loss_native`` as the loss, only the three basicts metrics and a finite ``null_val``; anything
+    else takes the base class's path as with ``native_tail=False`` (the default)."""
 
     class NativeRunner(base):
         native_hooks = True
@@ -296,11 +303,75 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
         def train_iters(self, epoch, iter_index, data):
             self._deferring, self._metric_cache = defer_meters, None
             try:
+                scaler = self._tail_scaler() if native_tail else None
+                if scaler is not None:
+                    return self._native_tail_iters(epoch, iter_index, data, scaler)
                 return super().train_iters(epoch, iter_index, data)
             finally:
                 self._deferring, self._metric_cache = False, None
 
         _NATIVE_METRICS = {"masked_mae": 0, "masked_rmse": 1, "masked_mape": 2}
+
+        # ---------------------------------------------------------------- the iteration's tail from one native call (native_tail=True)
+        def _is_basicts_metric(self, f):
+            return (getattr(f, "__name__", None) in self._NATIVE_METRICS
+                    and str(getattr(f, "__module__", "")).startswith("basicts.metrics"))
+
+        def _tail_scaler(self):
+            """(mean, std) when everything known BEFORE the forward pass allows the native tail, else None"""
+            model = _unwrap(self.model)
+            if not (isinstance(model, STEP) and next(model.parameters()).is_cuda):
+                return None
+            scaler = getattr(self, "scaler", None)
+            if not isinstance(scaler, dict):
+                return None
+            func, args = scaler.get("func"), scaler.get("args") or {}
+            if getattr(func, "__name__", func) != "re_standard_transform":
+                return None
+            mean, std = args.get("mean"), args.get("std")
+            if isinstance(mean, bool) or isinstance(std, bool) or not (isinstance(mean, numbers.Real) and isinstance(std, numbers.Real)):
+                return None
+            if getattr(self.loss, "__name__", None) not in ("step_loss", "step_loss_native"):
+                return None
+            metrics = getattr(self, "metrics", None)
+            if not isinstance(metrics, dict) or not all(self._is_basicts_metric(f) for f in metrics.values()):
+                return None
+            nv = getattr(self, "null_val", 0.0)
+            if not (isinstance(nv, numbers.Real) and math.isfinite(nv)):
+                return None
+            return float(mean), float(std)
+
+        def _native_tail_iters(self, epoch, iter_index, data, scaler):
+            """base_tsf_runner.py:237-255 with the rescaling, the curriculum slice, the loss and the three metrics in one train_tail call"""
+            from .step_loss import train_tail
+            mean, std = scaler
+            iter_num = (epoch - 1) * self.iter_per_epoch + iter_index
+            forward_return = list(self.forward(data=data, epoch=epoch, iter_num=iter_num, train=True))
+            cl = self.curriculum_learning(epoch=epoch) if getattr(self, "cl_param", None) else None
+            ok = len(forward_return) == 5
+            if ok:
+                pred, real, theta, prior, coef = forward_return
+                ok = (torch.is_tensor(pred) and torch.is_tensor(real) and pred.is_cuda and real.is_cuda and pred.dtype == torch.float32
+                      and real.dtype == torch.float32 and pred.dim() == 4 and pred.shape[3] == 1 and pred.shape == real.shape
+                      and pred.shape[1] <= 64 and torch.is_tensor(theta) and theta.is_cuda and theta.dtype == torch.float32
+                      and torch.is_tensor(prior) and not torch.is_tensor(coef) and (cl is None or 1 <= cl <= pred.shape[1]))
+            if not ok:
+                # the forward pass is done and cannot be repeated: the base class's tail (:240-254) on torch ops, the scaler being
+                # re_standard_transform with scalar mean / std (basicts/data/transform.py:59-65)
+                forward_return[0] = forward_return[0] * std + mean
+                forward_return[1] = forward_return[1] * std + mean
+                if cl is not None:
+                    forward_return[0] = forward_return[0][:, :cl, :, :]
+                    forward_return[1] = forward_return[1][:, :cl, :, :]
+                loss = self.metric_forward(self.loss, forward_return)
+                for metric_name, metric_func in self.metrics.items():
+                    metric_item = self.metric_forward(metric_func, forward_return[:2])
+                    self.update_epoch_meter("train_" + metric_name, metric_item.item())
+                return loss
+            loss, three = train_tail(pred, real, theta, prior, coef, null_val=float(self.null_val), rescale=(mean, std), horizons=cl)
+            for metric_name, metric_func in self.metrics.items():
+                self.update_epoch_meter("train_" + metric_name, _Deferred(three[self._NATIVE_METRICS[metric_func.__name__]]))
+            return loss
 
         def metric_forward(self, metric_func, args):
             if self._deferring and metric_func is not self.loss and native_metrics:

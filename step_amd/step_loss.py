@@ -80,14 +80,113 @@ class _NativeStepLoss(torch.autograd.Function):
         return op.view(ctx.shapes[0]), None, ot.view(ctx.shapes[1]), None, None, None, None, None
 
 
-def step_loss_native(prediction, real_value, theta, priori_adj, gsl_coefficient, null_val=0.0, rescale=None):
+def step_loss_native(prediction, real_value, theta, priori_adj, gsl_coefficient, null_val=0.0, rescale=None, horizons=None):
     """Same signature and value as ``step_loss`` (finite ``null_val``), computed by libstep_hip.
     ``rescale=(mean, std)``: ``prediction`` / ``real_value`` are the NORMALISED tensors and the loss is taken on ``x * std + mean`` --
     the runner's inverse scaling (base_tsf_runner.py:240-250, step_runner.py:86-92) done inside the loss kernels instead of four
     element-wise launches before them and their autograd nodes after; ``real_value`` may be one feature of the batch tensor
-    (``future[..., :1]``), it is read in place."""
+    (``future[..., :1]``), it is read in place.
+    ``horizons=k``: the loss of ``train_tail`` on the first ``k`` horizon steps of the FULL tensors (curriculum learning)."""
+    if horizons is not None:
+        return train_tail(prediction, real_value, theta, priori_adj, gsl_coefficient, null_val=null_val, rescale=rescale, horizons=horizons)[0]
     mean, std = (0.0, 1.0) if rescale is None else rescale
     return _NativeStepLoss.apply(prediction, real_value, theta, priori_adj, gsl_coefficient, null_val, std, mean)
+
+
+def _bhn_strides(x):
+    """element strides (b, h, n) of a [B, H, N] / [B, H, N, 1] tensor as libstep_hip takes them (all positive), or None"""
+    st = x.stride()[:3]
+    return tuple(int(v) for v in st) if all(v >= 1 for v in st) else None
+
+
+_TAIL_WORK = {}
+
+
+def _tail_work(device):
+    """the work buffer of ``step_train_tail`` of (device, current stream): allocated zeroed once, kept clean by the kernels; two
+    streams never share one"""
+    from . import _lib
+    key = (device.index, torch.cuda.current_stream().cuda_stream)          # (like every call of this package: the current device's stream)
+    w = _TAIL_WORK.get(key)
+    if w is None:
+        w = _TAIL_WORK[key] = torch.zeros(_lib.lib().step_train_tail_work_doubles(), dtype=torch.float64, device=device)
+    return w
+
+
+class _TrainTail(torch.autograd.Function):
+    """loss, both gradients and the three meters on the first k horizons from the two launches of libstep_hip step_train_tail; the
+    backward multiplies the gradients by the incoming one in one more (step_scale2)"""
+
+    @staticmethod
+    def forward(ctx, prediction, real_value, theta, priori_adj, coef, null_val, scale, shift, k):
+        from . import _lib
+        B, H, N = prediction.shape[:3]
+        p, r = prediction.detach(), real_value.detach()
+        ps, rs = _bhn_strides(p), _bhn_strides(r)
+        if ps is None:
+            p = p.contiguous()
+            ps = _bhn_strides(p)
+        if rs is None:
+            r = r.contiguous()
+            rs = _bhn_strides(r)
+        t = theta.detach().contiguous()
+        a = priori_adj.detach().contiguous().float()
+        dev = p.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        metrics = torch.empty(3, device=dev, dtype=torch.float32)
+        dp = torch.empty((B, H, N), device=dev, dtype=torch.float32)
+        dt = torch.empty_like(t)
+        _lib.call("step_train_tail", ctypes.c_void_p(p.data_ptr()), *ps, ctypes.c_void_p(r.data_ptr()), *rs, B, H, N, int(k), float(scale),
+                  float(shift), float(null_val), _lib.ptr(t), _lib.ptr(a), t.numel(), float(coef), _lib.ptr(_tail_work(dev)), _lib.ptr(loss),
+                  _lib.ptr(metrics), _lib.ptr(dp), _lib.ptr(dt), _lib.stream())
+        ctx.save_for_backward(dp, dt)
+        ctx.shapes = (prediction.shape, theta.shape)
+        ctx.mark_non_differentiable(metrics)
+        ctx.set_materialize_grads(False)          # (no zeros launch for the metrics' absent gradient)
+        return loss, metrics
+
+    @staticmethod
+    def backward(ctx, g, _g_metrics):
+        from . import _lib
+        if g is None:
+            return (None,) * 9
+        dp, dt = ctx.saved_tensors
+        if g.is_cuda and g.dtype == torch.float32 and g.numel() == 1:
+            op, ot = torch.empty_like(dp), torch.empty_like(dt)
+            _lib.call("step_scale2", _lib.ptr(dp), dp.numel(), _lib.ptr(dt), dt.numel(), _lib.ptr(g.contiguous()), _lib.ptr(op), _lib.ptr(ot),
+                      _lib.stream())
+        else:
+            op, ot = dp * g, dt * g
+        return op.view(ctx.shapes[0]), None, ot.view(ctx.shapes[1]), None, None, None, None, None, None
+
+
+def train_tail(prediction, real_value, theta, priori_adj, gsl_coefficient, null_val=0.0, rescale=None, horizons=None):
+    """-> ``(loss, metrics)``: the tail of one training iteration of the reference's runner under curriculum learning
+    (base_tsf_runner.py:237-254 with :170-190) from two launches of libstep_hip.  ``loss`` is ``step_loss`` on the first ``horizons``
+    horizon steps of ``prediction * std + mean`` / ``real_value * std + mean`` (``rescale=(mean, std)``; None: as they are),
+    differentiable w.r.t. ``prediction`` (the gradient has the prediction's FULL shape, exact zeros on the excluded horizons) and
+    ``theta``; ``metrics`` is an f32 ``[3]`` tensor (masked MAE, RMSE, MAPE of basicts/metrics on the same slice), no gradient.
+    ``prediction`` / ``real_value``: f32 device tensors of one shape ``[B, H, N, 1]`` (or ``[B, H, N]``), NOT sliced; ``real_value`` may
+    be one feature of the batch tensor (``future[..., :1]``): it is read in place, nothing is rescaled, sliced or copied.
+    ``horizons=None``: all of them.  ``null_val`` must be finite; a tensor ``gsl_coefficient`` (the graph-captured step) is not
+    supported here."""
+    if torch.is_tensor(gsl_coefficient):
+        raise ValueError("train_tail: a device-resident gsl_coefficient (GraphedTrainStep) is not supported")
+    if not (torch.is_tensor(prediction) and torch.is_tensor(real_value) and prediction.is_cuda and real_value.is_cuda
+            and prediction.dtype == torch.float32 and real_value.dtype == torch.float32 and prediction.shape == real_value.shape
+            and (prediction.dim() == 3 or (prediction.dim() == 4 and prediction.shape[3] == 1)) and prediction.numel() > 0):
+        raise ValueError("train_tail: prediction and real_value must be f32 device tensors of one shape [B, H, N, 1] or [B, H, N]")
+    if not (theta.is_cuda and theta.dtype == torch.float32 and theta.numel() == priori_adj.numel() > 0):
+        raise ValueError("train_tail: theta must be an f32 device tensor with as many elements as priori_adj")
+    H = prediction.shape[1]
+    k = H if horizons is None else int(horizons)
+    if not 1 <= k <= H or H > 64:
+        raise ValueError(f"train_tail: horizons = {horizons} is not in 1..{H} (at most 64 horizon steps)")
+    null_val = float(null_val)
+    if null_val != null_val or null_val in (float("inf"), float("-inf")):
+        raise ValueError("train_tail: null_val must be finite")
+    mean, std = (0.0, 1.0) if rescale is None else rescale
+    return _TrainTail.apply(prediction, real_value, theta, priori_adj, float(gsl_coefficient), null_val, float(std), float(mean), k)
 
 
 def step_loss(prediction, real_value, theta, priori_adj, gsl_coefficient, null_val=np.nan):
