@@ -573,6 +573,29 @@ int step_train_tail(const float* pred, long p_sb, long p_sh, long p_sn, const fl
                     int N, int k, float scale, float shift, float null_val, const float* theta, const float* prior, long n_adj, float coef,
                     double* work, float* loss, float* metrics, float* dpred, float* dtheta, void* stream);
 
+/* ---------------------------------------------------------------- pre-training tail -------
+ * The tail of one TSFormer pre-training iteration in two launches: masked_mae (basicts/metrics/mae.py) on the RESCALED reconstruction of
+ * the masked tokens and their labels, its gradient, and the three training meters of base_tsf_runner.py:252-254 -- instead of the
+ * slice + reshape of the decoder's output, the advanced-index gather of the labels (step/step_arch/tsformer/tsformer.py:152-158), the two
+ * re_standard_transform calls, the loss, the three metric functions and their autograd nodes, which scatter the gradient back into a
+ * zero-filled [S, P, 12] tensor (additive to ABI 10).
+ *  r            f32 [S, P, 12] contiguous, NORMALISED: the decoder's output; rows 0 .. Pu - 1 of a sequence (Pu = P - Pm) belong to the
+ *               unmasked tokens, row Pu + j is the reconstruction of masked token j
+ *  series       f32 [S, P * 12], the layout of step_pack_long_history / step_gather_windows: the label of masked token j is the patch
+ *               series[s, mk[j] * 12 .. mk[j] * 12 + 11]
+ *  mk           int32 [Pm] on the device, any order, values in 0 .. P - 1 (not checked)
+ *               the terms are taken on x * scale + shift, rounded twice as torch does
+ *  work         f64 [step_pretrain_tail_work_doubles()], zero before the FIRST call, then left to the calls of ONE stream (the scheme
+ *               of step_train_tail: two halves used by alternate calls, no memset is queued)
+ *  loss         f32 [1] = S_abs / cnt, m = !(|y - null_val| <= 5e-5) (null_val finite); 0 when cnt == 0
+ *  metrics      f32 [3] = MAE, RMSE, MAPE with the definitions of step_eval_metrics_accumulate (a NaN term adds 0 and still counts)
+ *  dr           f32 [S, P, 12], ALL of it written: sign(p - y) * scale / cnt at the counted elements of the masked rows; exactly 0 in
+ *               rows < Pu, at masked labels and at NaN differences.  NULL: the values only (validation)
+ * r, series and dr are read and written as 16-byte vectors (a token is three of them) and must be 16-byte aligned.  S * P * 12 < 2^31. */
+long step_pretrain_tail_work_doubles(void);          /* pure host function */
+int step_pretrain_tail(const float* r, const float* series, const int* mk, int S, int P, int Pm, float scale, float shift, float null_val,
+                       double* work, float* loss, float* metrics, float* dr, void* stream);
+
 /* ---------------------------------------------------------------- self test --------------
  * Verifies on the device the MFMA operand/accumulator lane maps this library is built on
  * (cdna_hip_programming.md section 3).  out: int32[8] failure counters, all zero when ok. */

@@ -169,6 +169,9 @@ _SIGS = {
     # loss, gradients and meters of a training iteration on the first k horizons (csrc/train_tail.hip)
     "step_train_tail_work_doubles": (_l, []),
     "step_train_tail": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _l, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # loss, gradient and meters of a pre-training iteration from the decoder's output and the packed series (csrc/pretrain_tail.hip)
+    "step_pretrain_tail_work_doubles": (_l, []),
+    "step_pretrain_tail": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -5,25 +5,13 @@
 // (basicts/runners/base_tsf_runner.py:237-254 with curriculum learning, :170-190; step/step_loss/step_loss.py:5-16;
 // basicts/metrics/{mae,rmse,mape}.py).
 //
-// Work buffer (f64, zeroed by the caller ONCE, then owned by the calls of one stream):
-//   [0, 6)    sums of the even calls   {S_abs, S_sq, cnt, S_ape, cnt0, S_bce}
-//   [6, 12)   sums of the odd calls
-//   12        index of the NEXT call (an unsigned 64-bit integer in the slot): written by a finish launch, read by the next reduce launch
-//   13        index of the CURRENT call: written by a reduce launch, read by its finish launch
-// Call n adds into half n & 1; its finish launch reads that half and clears the other one for call n + 1, so no memset is queued.
-// Inside a launch the workgroups meet only in the atomic adds; whatever reads a sum or an index does so in a LATER launch of the same
-// stream, and no word is both written and read inside one launch.
-#include "common.h"
+// The work buffer and the device helpers are those of csrc/tail_device.h.
+#include "tail_device.h"
 #include <limits.h>
 
 namespace {
 
-constexpr int TT_THREADS = 256;          // four waves per workgroup
-constexpr int TT_WAVES = TT_THREADS / 64;
 constexpr int TT_MAX_H = 64;
-constexpr int TT_SUMS = 6;
-constexpr int TT_NEXT = 2 * TT_SUMS, TT_CUR = 2 * TT_SUMS + 1;
-constexpr long TT_WORK_DOUBLES = 2 * TT_SUMS + 2;
 
 struct TailArgs {
     const float* pred; long p_sb, p_sh, p_sn;
@@ -34,17 +22,8 @@ struct TailArgs {
     double* work;
 };
 
-// The rescaling must round twice, like torch's `x * std + mean`: a label ONE float32 step across the 5e-5 / 1e-4 thresholds changes its
-// mask (csrc/eval_metrics.hip has the whole story).  Contraction is off in every function that rescales, and the arithmetic is written
-// with plain operators.
-struct TailElem { float p, y; bool m; };
 __device__ __forceinline__ TailElem tail_elem(const TailArgs& a, long b, long h, long n) {
-#pragma clang fp contract(off)
-    TailElem e;
-    e.p = a.pred[b * a.p_sb + h * a.p_sh + n * a.p_sn] * a.scale + a.shift;
-    e.y = a.real[b * a.r_sb + h * a.r_sh + n * a.r_sn] * a.scale + a.shift;
-    e.m = !(fabsf(e.y - a.null_val) <= 5e-5f);          // mae.py:17-21: ~isclose(y, null, atol = 5e-5, rtol = 0); a NaN label counts
-    return e;
+    return tail_rescale(a.pred[b * a.p_sb + h * a.p_sh + n * a.p_sn], a.real[b * a.r_sb + h * a.r_sh + n * a.r_sn], a.scale, a.shift, a.null_val);
 }
 
 // Launch 1.  Grid-stride over the B * k * N included elements (consecutive lanes read consecutive n) and over the n_adj edges; f32 terms
@@ -60,37 +39,14 @@ __global__ __launch_bounds__(TT_THREADS) void train_tail_reduce_kernel(TailArgs 
     const long n1 = (long)a.B * kn;
     for (long i = first; i < n1; i += stride) {
         const unsigned b = (unsigned)i / kn, r = (unsigned)i - b * kn, h = r / (unsigned)a.N, n = r - h * (unsigned)a.N;
-        const TailElem e = tail_elem(a, b, h, n);
-        if (e.m) {
-            const float d = e.p - e.y, ad = fabsf(d), sq = d * d;
-            if (!isnan(ad)) s[0] += (double)ad;          // where(isnan(loss), 0, loss), mae.py:27: the element still counts
-            if (!isnan(sq)) s[1] += (double)sq;
-            s[2] += 1.0;
-        }
-        // mape.py:20-35: labels below 1e-4 become 0, the null value is 0 whatever the caller's
-        const float y0 = fabsf(e.y) < 1e-4f ? 0.f : e.y;
-        if (!(fabsf(y0) <= 5e-5f)) {
-            const float t = fabsf(fabsf(e.p - y0) / y0);
-            if (!isnan(t)) s[3] += (double)t;
-            s[4] += 1.0;
-        }
+        tail_accumulate(tail_elem(a, b, h, n), s);
     }
     for (long i = first; i < a.n_adj; i += stride) {
         const float t = a.theta[i], y = a.prior[i];
         const float l1 = fmaxf(logf(t), -100.f), l0 = fmaxf(logf(1.f - t), -100.f);      // torch's BCELoss clamps the logs at -100
         s[5] -= (double)(y * l1 + (1.f - y) * l0);
     }
-#pragma unroll
-    for (int j = 0; j < TT_SUMS; ++j)
-        for (int o = 32; o > 0; o >>= 1) s[j] += __shfl_xor(s[j], o, 64);
-    if ((threadIdx.x & 63) == 0)
-        for (int j = 0; j < TT_SUMS; ++j) red[threadIdx.x >> 6][j] = s[j];
-    __syncthreads();
-    if (threadIdx.x < TT_SUMS) {
-        const int j = threadIdx.x;
-        atomicAdd(a.work + (call & 1) * TT_SUMS + j, red[0][j] + red[1][j] + red[2][j] + red[3][j]);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) reinterpret_cast<unsigned long long*>(a.work)[TT_CUR] = call;
+    tail_block_add(s, red, a.work, call);
 }
 
 // Launch 2.  Every workgroup reads the finished sums; block 0 writes the loss and the metrics, clears the other half and advances the call
@@ -103,15 +59,7 @@ __global__ __launch_bounds__(TT_THREADS) void train_tail_finish_kernel(TailArgs 
     const double* sum = a.work + (call & 1) * TT_SUMS;
     const double cnt = sum[2];
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        const double cnt0 = sum[4];
-        const float mae = cnt > 0.0 ? (float)(sum[0] / cnt) : 0.f;
-        *loss = mae + coef * (float)(sum[5] / (double)a.n_adj);
-        metrics[0] = mae;
-        metrics[1] = cnt > 0.0 ? (float)sqrt(sum[1] / cnt) : 0.f;
-        metrics[2] = cnt0 > 0.0 ? (float)(sum[3] / cnt0) : 0.f;
-        double* other = a.work + ((call + 1) & 1) * TT_SUMS;
-        for (int j = 0; j < TT_SUMS; ++j) other[j] = 0.0;
-        reinterpret_cast<unsigned long long*>(a.work)[TT_NEXT] = call + 1;
+        *loss = tail_finish_values(sum, a.work, call, metrics) + coef * (float)(sum[5] / (double)a.n_adj);
     }
     const float g = cnt > 0.0 ? (float)(1.0 / cnt) * a.scale : 0.f;      // d/d pred of the mean on pred * scale + shift
     const long stride = (long)gridDim.x * TT_THREADS, first = (long)blockIdx.x * TT_THREADS + threadIdx.x;
@@ -120,11 +68,7 @@ __global__ __launch_bounds__(TT_THREADS) void train_tail_finish_kernel(TailArgs 
     for (long i = first; i < n_all; i += stride) {
         const unsigned b = (unsigned)i / hn, r = (unsigned)i - b * hn, h = r / (unsigned)a.N, n = r - h * (unsigned)a.N;
         float v = 0.f;
-        if (h < (unsigned)a.k) {
-            const TailElem e = tail_elem(a, b, h, n);
-            const float d = e.p - e.y;                                   // a NaN difference compares false twice: gradient 0
-            if (e.m) v = d > 0.f ? g : (d < 0.f ? -g : 0.f);
-        }
+        if (h < (unsigned)a.k) v = tail_sign_grad(tail_elem(a, b, h, n), g);
         dpred[i] = v;
     }
     const float sc = coef / (float)a.n_adj;

@@ -28,6 +28,10 @@ implementation and only changes WHERE the data lives and WHEN the host reads num
 * ``init_training`` swaps the ``torch.optim.Adam`` + ``clip_grad_norm_`` pair the config asks for (``STEP_PEMS04.py:89-106``) for
   ``step_amd.optim.FusedAdamClip`` with the same hyper-parameters (one pass over the flat buffers); any other optimizer is left alone.
 
+The pre-training stage (``step/TSFormer_*.py``) has the same slots: ``native_runner(TSFormerRunner, native_pretrain=True)`` and
+``CFG.DATASET_CLS = DevicePretrainingDataset`` (index-only ``(future_data, LongHistoryRef)`` batches, fused clip + Adam, loss + gradient +
+meters of an iteration from one ``TSFormer.pretrain_tail`` call).
+
 Nothing here imports the reference or easytorch: the base class is handed in by the config file, which lives in the reference tree.
 """
 import math
@@ -35,10 +39,12 @@ import numbers
 import os
 import pickle
 
+import numpy as np
 import torch
 from torch.utils.data import Dataset
 
 from .step_arch.step import STEP, DeviceWindowLoader, LongHistoryRef
+from .step_arch.tsformer import TSFormer
 
 
 def _unwrap(model):
@@ -100,6 +106,67 @@ class DeviceForecastingDataset(Dataset):
         return self._loaders[key]
 
 
+class DevicePretrainingDataset(Dataset):
+    """Drop-in for the reference's ``PretrainingDataset`` (``step/step_data/pretraining_dataset.py``, which is basicts'
+    ``TimeSeriesForecastingDataset``: the same three constructor arguments, the same files, the same length) whose samples are FORECAST
+    ORIGINS, like ``DeviceForecastingDataset``'s: ``__getitem__`` returns the int64 scalar ``idx[1]``, and ``LookaheadLoader`` turns a
+    batch of them into ``(future_data, LongHistoryRef)`` -- the pair ``TSFormerRunner.forward`` unpacks
+    (``step/step_runner/tsformer_runner.py:57``) -- over the series, which is moved to the device once.  The long history of a window
+    (2016 or 4032 rows of every sensor, 126 MB per batch of 16 at PEMS-BAY) is never built: ``TSFormer`` gathers its input from the
+    reference.  The window lengths are the index's own (``CFG.DATASET_INPUT_LEN`` / ``CFG.DATASET_OUTPUT_LEN`` when it was generated)."""
+
+    index_only = True
+
+    def __init__(self, data_file_path, index_file_path, mode):
+        super().__init__()
+        assert mode in ["train", "valid", "test"], "error mode"
+        for p, what in ((data_file_path, "data"), (index_file_path, "index")):
+            if not os.path.isfile(p):
+                raise FileNotFoundError("BasicTS can not find {0} file {1}".format(what, p))
+        with open(data_file_path, "rb") as f:
+            self.data = torch.from_numpy(pickle.load(f)["processed_data"]).float()
+        with open(index_file_path, "rb") as f:
+            self.index = pickle.load(f)[mode]
+        try:
+            idx = np.asarray(self.index, dtype=np.int64)
+        except (ValueError, TypeError):
+            idx = None
+        if idx is None or idx.ndim != 2 or idx.shape[1] != 3 or idx.shape[0] == 0:
+            # (history start, forecast origin, future end): the history ends where the future starts
+            raise ValueError("DevicePretrainingDataset needs an index of (start, origin, end) triples of contiguous windows")
+        self.history_len, self.future_len = int(idx[0, 1] - idx[0, 0]), int(idx[0, 2] - idx[0, 1])
+        bad = np.nonzero((idx[:, 1] - idx[:, 0] != self.history_len) | (idx[:, 2] - idx[:, 1] != self.future_len))[0]
+        if self.history_len <= 0 or self.future_len <= 0 or bad.size:
+            which = f"entry {int(bad[0])} = {tuple(int(v) for v in idx[bad[0]])}" if bad.size else f"entry 0 = {tuple(int(v) for v in idx[0])}"
+            raise ValueError(f"DevicePretrainingDataset: index {which} does not have the window lengths "
+                             f"({self.history_len}, {self.future_len}) of the first entry (both positive)")
+        self._loaders = {}
+
+    def __getstate__(self):          # DataLoader workers get the index and the host series, never the device copies
+        d = dict(self.__dict__)
+        d["_loaders"] = {}
+        return d
+
+    def __getitem__(self, index):
+        return torch.tensor(int(self.index[index][1]), dtype=torch.int64)
+
+    def __len__(self):
+        return len(self.index)
+
+    def windows(self, origins, device, host_origins=None):
+        """int64 [B] forecast origins -> (future_data [B,H,N,C], LongHistoryRef [B,L,N,C]) on ``device``; ``host_origins`` as in
+        ``DeviceForecastingDataset.windows``"""
+        _, long_ref, fut = self.device_loader(device).batch(origins, t0_host=None if host_origins is None else host_origins.tolist())
+        return fut, long_ref
+
+    def device_loader(self, device):
+        """the dataset's ``DeviceWindowLoader`` on ``device``: the series is moved there once"""
+        key = (device.type, device.index)
+        if key not in self._loaders:
+            self._loaders[key] = DeviceWindowLoader(self.data.to(device), self.history_len, self.future_len)
+        return self._loaders[key]
+
+
 class LookaheadLoader:
     """Iterates ``loader`` one batch ahead of its consumer (see the module docstring).  ``runner`` supplies the device
     (``to_running_device``) and the model; ``prefetch=False`` only stages the batches on the device."""
@@ -122,7 +189,8 @@ class LookaheadLoader:
         return p.device
 
     def _stage(self, batch):
-        """host batch -> device batch, without making the host wait: (future, history, long history)"""
+        """host batch -> device batch, without making the host wait: (future, history, long history), or whatever tuple an index-only
+        dataset's ``windows`` makes of a batch of origins"""
         dev = self._device()
         self.staged_batches += 1
         if torch.is_tensor(batch) and batch.dim() == 1 and getattr(self.dataset, "index_only", False):
@@ -188,7 +256,7 @@ class _Deferred:
 
 
 def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, encoder_workgroups=None, native_metrics=True,
-                  eval_cache_bytes=0, native_tail=False):
+                  eval_cache_bytes=0, native_tail=False, native_pretrain=False):
     """-> subclass of ``base`` (the reference's ``STEPRunner``, or any ``BaseTimeSeriesForecastingRunner``) for ``CFG.RUNNER``.
     ``encoder_workgroups``: compute units of the persistent encoder launch next to the step (None: 160 at 307 nodes / 336 tokens, the
     measured optimum of config C2; 0: one workgroup per sequence) -- only used while batches are prefetched.
@@ -200,7 +268,13 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
     on the model's normalised prediction and the batch's target view -- no rescale, no ``[:, :cl_length]`` slice, no copy -- also under
     curriculum learning (``CFG.TRAIN.CL``).  Needs a ``STEP`` module on a GPU, the ``re_standard_transform`` scaler with scalar
     mean / std, ``step_loss`` / ``step_loss_native`` as the loss, only the three basicts metrics and a finite ``null_val``; anything
-    else takes the base class's path as with ``native_tail=False`` (the default)."""
+    else takes the base class's path as with ``native_tail=False`` (the default).
+    ``native_pretrain``: for ``TSFormerRunner`` (``step/TSFormer_*.py``) around a ``TSFormer`` in pre-train mode on a GPU, not wrapped:
+    ``init_training`` flattens the module's parameters and swaps ``torch.optim.Adam`` + ``clip_grad_norm_`` for ``FusedAdamClip`` (under
+    the conditions of the STEP branch), and ``train_iters`` / ``val_iters`` take the loss, its gradient and the three meters from ONE
+    ``TSFormer.pretrain_tail`` call (validation under ``no_grad``, nothing read back).  That needs the ``re_standard_transform`` scaler
+    with scalar mean / std, ``masked_mae`` (basicts' or this package's) as the loss, only the three basicts metrics, a finite
+    ``null_val`` and no ``CFG.TRAIN.CL``; anything else takes the base class's path as with ``native_pretrain=False`` (the default)."""
 
     class NativeRunner(base):
         native_hooks = True
@@ -277,11 +351,18 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             return super().select_target_features(data)
 
         # ---------------------------------------------------------------- optimizer
+        def _pretrain_module(self):
+            """the TSFormer that ``native_pretrain`` acts on, or None"""
+            model = self.model
+            ok = (native_pretrain and isinstance(model, TSFormer) and model.mode == "pre-train" and next(model.parameters()).is_cuda)
+            return model if ok else None
+
         def init_training(self, cfg):
             super().init_training(cfg)
             model = _unwrap(self.model)
             opt = getattr(self, "optim", None)
-            if not (fused_optimizer and isinstance(model, STEP) and model is self.model and type(opt) is torch.optim.Adam
+            pretrain = self._pretrain_module() is not None
+            if not (fused_optimizer and (isinstance(model, STEP) or pretrain) and model is self.model and type(opt) is torch.optim.Adam
                     and next(model.parameters()).is_cuda):
                 return          # (under a DistributedDataParallel wrap the reducer owns the .grad tensors: torch's optimizer stays)
             from .optim import FusedAdamClip
@@ -291,8 +372,10 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             clip = getattr(self, "clip_grad_param", None) or {}
             if clip and float(clip.get("norm_type", 2.0)) != 2.0:
                 return
+            if pretrain:
+                model.flatten_parameters()          # (values and state_dict unchanged: every parameter becomes a view into one buffer)
             fused = FusedAdamClip(model, lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"],
-                                  max_norm=clip.get("max_norm"), param_grads=False)
+                                  max_norm=clip.get("max_norm"), param_grads=pretrain)
             sched = getattr(self, "scheduler", None)
             if sched is not None:
                 s = cfg["TRAIN"].get("LR_SCHEDULER")
@@ -306,6 +389,12 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                 scaler = self._tail_scaler() if native_tail else None
                 if scaler is not None:
                     return self._native_tail_iters(epoch, iter_index, data, scaler)
+                scaler = self._pretrain_scaler(data) if native_pretrain else None
+                if scaler is not None:
+                    loss, three = self._pretrain_tail(data, scaler)
+                    for metric_name, metric_func in self.metrics.items():
+                        self.update_epoch_meter("train_" + metric_name, _Deferred(three[self._NATIVE_METRICS[metric_func.__name__]]))
+                    return loss
                 return super().train_iters(epoch, iter_index, data)
             finally:
                 self._deferring, self._metric_cache = False, None
@@ -322,6 +411,11 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             model = _unwrap(self.model)
             if not (isinstance(model, STEP) and next(model.parameters()).is_cuda):
                 return None
+            return self._scalar_rescale(("step_loss", "step_loss_native"))
+
+        def _scalar_rescale(self, loss_names):
+            """(mean, std) of a ``re_standard_transform`` scaler with scalar arguments when the loss is one of ``loss_names``, the metrics
+            are the three of basicts and ``null_val`` is finite, else None"""
             scaler = getattr(self, "scaler", None)
             if not isinstance(scaler, dict):
                 return None
@@ -331,7 +425,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             mean, std = args.get("mean"), args.get("std")
             if isinstance(mean, bool) or isinstance(std, bool) or not (isinstance(mean, numbers.Real) and isinstance(std, numbers.Real)):
                 return None
-            if getattr(self.loss, "__name__", None) not in ("step_loss", "step_loss_native"):
+            if getattr(self.loss, "__name__", None) not in loss_names:
                 return None
             metrics = getattr(self, "metrics", None)
             if not isinstance(metrics, dict) or not all(self._is_basicts_metric(f) for f in metrics.values()):
@@ -340,6 +434,31 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             if not (isinstance(nv, numbers.Real) and math.isfinite(nv)):
                 return None
             return float(mean), float(std)
+
+        # ---------------------------------------------------------------- TSFormer pre-training (native_pretrain=True)
+        def _pretrain_scaler(self, data):
+            """(mean, std) when everything known BEFORE the forward pass allows ``TSFormer.pretrain_tail``, else None"""
+            if self._pretrain_module() is None or getattr(self, "cl_param", None):
+                return None
+            if not (isinstance(data, (tuple, list)) and len(data) == 2):          # (future_data, history_data), tsformer_runner.py:57
+                return None
+            if not str(getattr(self.loss, "__module__", "")).startswith(("basicts.", "step_amd.")):
+                return None
+            return self._scalar_rescale(("masked_mae", "masked_mae_native"))
+
+        def _pretrain_tail(self, data, scaler):
+            """tsformer_runner.py:57-65 and base_tsf_runner.py:240-254 (:266-273 in validation) from one pretrain_tail call"""
+            history_data = self.select_input_features(self.to_running_device(data[1]))
+            return self.model.pretrain_tail(history_data, null_val=float(self.null_val), rescale=scaler)
+
+        def val_iters(self, iter_index, data):
+            scaler = self._pretrain_scaler(data) if native_pretrain else None
+            if scaler is None:
+                return super().val_iters(iter_index, data)
+            with torch.no_grad():
+                _, three = self._pretrain_tail(data, scaler)
+            for metric_name, metric_func in self.metrics.items():          # fed with the other deferred values when the epoch's meters are printed
+                self.update_epoch_meter("val_" + metric_name, _Deferred(three[self._NATIVE_METRICS[metric_func.__name__]]))
 
         def _native_tail_iters(self, epoch, iter_index, data, scaler):
             """base_tsf_runner.py:237-255 with the rescaling, the curriculum slice, the loss and the three metrics in one train_tail call"""
@@ -417,6 +536,10 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
         def plt_epoch_meters(self, meter_type, step):
             self.flush_meters()
             return super().plt_epoch_meters(meter_type, step)
+
+        def on_validating_end(self, *args, **kwargs):
+            self.flush_meters()          # (base_tsf_runner.py:321-329 picks the best model by the epoch's val_MAE)
+            return super().on_validating_end(*args, **kwargs)
 
     NativeRunner.__name__ = "Native" + base.__name__
     NativeRunner.__qualname__ = NativeRunner.__name__

@@ -454,6 +454,55 @@ class _PretrainFunction(torch.autograd.Function):
         return (None, None, None, None) + tuple(G[n] for n in model._pt_names)
 
 
+_PT_TAIL_WORK = {}
+
+
+def _pt_tail_work(device):
+    """the work buffer of ``step_pretrain_tail`` of (device, current stream): allocated zeroed once, kept clean by the kernels; two
+    streams never share one"""
+    key = (device.index, torch.cuda.current_stream().cuda_stream)
+    w = _PT_TAIL_WORK.get(key)
+    if w is None:
+        w = _PT_TAIL_WORK[key] = torch.zeros(_lib.lib().step_pretrain_tail_work_doubles(), dtype=torch.float64, device=device)
+    return w
+
+
+class _PretrainTail(torch.autograd.Function):
+    """loss, its gradient w.r.t. the decoder's output r [S, P, 12] and the three meters from the two launches of libstep_hip
+    step_pretrain_tail; the backward multiplies the gradient by the incoming one in one more (step_scale2) and hands it to
+    _PretrainFunction.backward in r's own layout"""
+
+    @staticmethod
+    def forward(ctx, r, series, mk, null_val, scale, shift, want_grad):
+        S, P, _ = r.shape
+        rc = r.detach().contiguous()
+        dev = rc.device
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        metrics = torch.empty(3, device=dev, dtype=torch.float32)
+        dr = torch.empty_like(rc) if want_grad else None          # (torch.no_grad(): the values only)
+        _lib.call("step_pretrain_tail", _lib.ptr(rc), _lib.ptr(series), _lib.ptr(mk), S, P, mk.numel(), float(scale), float(shift),
+                  float(null_val), _lib.ptr(_pt_tail_work(dev)), _lib.ptr(loss), _lib.ptr(metrics), _lib.ptr(dr), _lib.stream())
+        if dr is not None:
+            ctx.save_for_backward(dr)
+        ctx.mark_non_differentiable(metrics)
+        ctx.set_materialize_grads(False)          # (no zeros launch for the metrics' absent gradient)
+        return loss, metrics
+
+    @staticmethod
+    def backward(ctx, g, _g_metrics):
+        if g is None:
+            return (None,) * 7
+        dr, = ctx.saved_tensors
+        if g.is_cuda and g.dtype == torch.float32 and g.numel() == 1:
+            # step_scale2 scales two arrays: the second one is the incoming gradient itself, one float
+            g = g.contiguous()
+            out, spare = torch.empty_like(dr), torch.empty(1, device=dr.device, dtype=torch.float32)
+            _lib.call("step_scale2", _lib.ptr(dr), dr.numel(), _lib.ptr(g), 1, _lib.ptr(g), _lib.ptr(out), _lib.ptr(spare), _lib.stream())
+        else:
+            out = dr * g
+        return out, None, None, None, None, None, None
+
+
 class TSFormer(nn.Module):
     """Drop-in for the reference TSFormer (forecasting mode: fused encoder kernel; pre-train mode: native forward + backward)."""
 
@@ -806,20 +855,59 @@ class TSFormer(nn.Module):
         self._seed_ctr2 += 1
         return (torch.initial_seed() * 6364136223846793005 + self._seed_ctr2 * 1442695040888963407) & ((1 << 63) - 1)
 
-    def _forward_pretrain(self, history_data):
-        """history_data [B, L, N, C] -> (reconstruction of the masked tokens [B, Pm*12, N], their labels [B, Pm*12, N])."""
+    def _pretrain_series(self, history_data):
+        """history_data [B, L, N, C] (a device tensor or a ``LongHistoryRef``) -> (series [B*N, L] of the selected feature, B, N, L)"""
         if not history_data.is_cuda:
             raise RuntimeError("step_amd.TSFormer runs only on an AMD GPU (no CPU fallback)")
+        from .step import LongHistoryRef          # (step.py imports this module)
         B, L, N, Cc = history_data.shape
+        if isinstance(history_data, LongHistoryRef):
+            # index-only loader: one gather straight from the resident series, no [B, L, N, C] tensor and no pack launch
+            d = history_data.data
+            series = torch.empty(B * N, L, device=d.device)
+            _lib.call("step_gather_windows", _lib.ptr(d), d.shape[0], d.shape[1], d.shape[2], history_data.channels[self.selected_feature],
+                      _lib.ptr(history_data.t0), B, L, 12, _lib.ptr(series), None, None, _lib.stream())
+            return series, B, N, L
         x = history_data.contiguous().float()
         series = torch.empty(B * N, L, device=x.device)
         _lib.call("step_pack_long_history", _lib.ptr(x), B, L, N, Cc, self.selected_feature, _lib.ptr(series), _lib.stream())
+        return series, B, N, L
+
+    def _pretrain_output(self, history_data):
+        """-> (r [S, P, 12] the decoder's output, series [S, L], masked indices int32 [Pm] on the device, (B, N, P, Pu))"""
+        series, B, N, L = self._pretrain_series(history_data)
         um_list, mk_list = self.mask()
-        um = torch.tensor(um_list, dtype=torch.int32, device=x.device)
-        mk = torch.tensor(mk_list, dtype=torch.int32, device=x.device)
-        P = L // self.patch_size
+        um = torch.tensor(um_list, dtype=torch.int32, device=series.device)
+        mk = torch.tensor(mk_list, dtype=torch.int32, device=series.device)
         r = _PretrainFunction.apply(self, series, um, mk, *self._pt_params())              # [S, P, 12]
-        Pu = len(um_list)
+        return r, series, mk, (B, N, L // self.patch_size, len(um_list))
+
+    def _forward_pretrain(self, history_data):
+        """history_data [B, L, N, C] -> (reconstruction of the masked tokens [B, Pm*12, N], their labels [B, Pm*12, N])."""
+        r, series, mk, (B, N, P, Pu) = self._pretrain_output(history_data)
         recon = r.view(B, N, P, self.patch_size)[:, :, Pu:, :].reshape(B, N, -1).transpose(1, 2)      # tsformer.py:153-154
         label = series.view(B, N, P, self.patch_size)[:, :, mk.long(), :].reshape(B, N, -1).transpose(1, 2)   # :156-158
         return recon, label
+
+    def pretrain_tail(self, history_data, null_val=0.0, rescale=None):
+        """-> ``(loss, metrics)``: the pre-training forward and the tail of the reference's iteration around it
+        (base_tsf_runner.py:237-254 on the outputs of tsformer.py:152-158) from two launches of libstep_hip.  ``loss`` is ``masked_mae`` on
+        ``recon * std + mean`` / ``label * std + mean`` (``rescale=(mean, std)``; None: as they are), differentiable w.r.t. the module's
+        parameters: its gradient reaches the native backward in the layout of the decoder's output, without the slice, gather, transpose
+        and zero-fill launches of the views ``forward()`` returns.  ``metrics`` is an f32 ``[3]`` tensor (masked MAE, RMSE, MAPE of
+        basicts/metrics on the same elements), no gradient.  ``history_data``: what ``forward()`` takes in pre-train mode, a device
+        tensor ``[B, L, N, C]`` or a ``LongHistoryRef``.  ``null_val`` must be finite.  Under ``torch.no_grad()`` only the values are
+        computed."""
+        if self.mode != "pre-train":
+            raise ValueError("TSFormer.pretrain_tail: the module is not in pre-train mode")
+        from .step import LongHistoryRef
+        if not (isinstance(history_data, LongHistoryRef) or (torch.is_tensor(history_data) and history_data.dim() == 4)):
+            raise ValueError("TSFormer.pretrain_tail: history_data must be a [B, L, N, C] device tensor or a LongHistoryRef")
+        null_val = float(null_val)
+        if null_val != null_val or null_val in (float("inf"), float("-inf")):
+            raise ValueError("TSFormer.pretrain_tail: null_val must be finite")
+        if not history_data.is_cuda:
+            raise RuntimeError("step_amd.TSFormer runs only on an AMD GPU (no CPU fallback)")
+        mean, std = (0.0, 1.0) if rescale is None else (float(rescale[0]), float(rescale[1]))
+        r, series, mk, _ = self._pretrain_output(history_data)
+        return _PretrainTail.apply(r, series, mk, null_val, std, mean, torch.is_grad_enabled() and r.requires_grad)
