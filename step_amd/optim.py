@@ -10,19 +10,143 @@ after the square root) preceded by ``torch.nn.utils.clip_grad_norm_``.  Paramete
 It consumes the flat gradient buffer of the LAST native backward (``model._flat_grad``): one backward per ``step()``, as in the
 reference's loop.  With gradient accumulation over several backwards use ``torch.optim.Adam`` on ``model.parameters()``
 (``bench.py --torch-optim``), which reads the accumulated ``.grad`` tensors.
+
+Checkpoints: ``state_dict()`` / ``load_state_dict()`` speak ``torch.optim.Adam``'s format (one ``{"step", "exp_avg", "exp_avg_sq"}``
+entry per parameter, indexed by the parameter's POSITION in the sequence ``params``), so a checkpoint written around either optimizer
+resumes around the other.  The two conversions are the plain functions ``moments_to_state`` / ``state_to_moments`` below (no library,
+no device needed).
 """
 import torch
 
 from . import _lib
 
 
+def flat_items(model):
+    """[(name, offset in floats, Parameter)] of the model's flat buffer, in buffer order: ``STEP._grad_layout()["items"]``, or the
+    ``_pt_names`` of a pre-training ``TSFormer`` (every parameter starts at a multiple of four floats)"""
+    if hasattr(model, "_pt_params"):
+        items, off = [], 0
+        for n, p in zip(model._pt_names, model._pt_params()):
+            items.append((n, off, p))
+            off += (p.numel() + 3) & ~3
+        return items
+    lay, tr = model._grad_layout(), dict(model._trainable())
+    return [(k, lay["items"][k][0], tr[k]) for k in lay["order"]]
+
+
+def index_flat_items(items, params, names=None):
+    """-> ({position in ``params``: (name, offset, Parameter)}, {position: name} of every entry of ``params``).  Parameters are matched
+    by identity; ``names`` maps id(Parameter) -> a name for the messages about parameters outside the flat buffer."""
+    params = list(params)
+    pos = {}
+    for i, p in enumerate(params):
+        pos.setdefault(id(p), i)
+    missing = [n for n, _, p in items if id(p) not in pos]
+    if missing:
+        raise ValueError(f"FusedAdamClip: params lacks {len(missing)} parameter(s) of the flat buffer (first: {missing[0]!r}): pass every "
+                         "parameter the native backward gives a gradient, in the order torch.optim.Adam would hold them")
+    index = {pos[id(p)]: (n, off, p) for n, off, p in items}
+    label = {i: index[i][0] if i in index else (names or {}).get(id(p), f"params[{i}]") for i, p in enumerate(params)}
+    return index, label
+
+
+def moments_to_state(index, exp_avg, exp_avg_sq, step):
+    """flat moment buffers -> the ``"state"`` of ``torch.optim.Adam.state_dict()``: per flat parameter two VIEWS into the buffers (no
+    copy, no synchronisation; ``torch.save`` writes the shared storage once) and ``step`` as torch keeps it, a 0-d float32 host tensor
+    of its own.  Empty before the first step, as torch's."""
+    if int(step) == 0:
+        return {}
+    state = {}
+    for i in sorted(index):
+        _, off, p = index[i]
+        n = p.numel()
+        state[i] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": exp_avg[off:off + n].view(p.shape),
+                    "exp_avg_sq": exp_avg_sq[off:off + n].view(p.shape)}
+    return state
+
+
+def _step_value(v):
+    v = float(v)          # an int, a float or a tensor on any device
+    if v != int(v) or v < 0:
+        raise ValueError(f"FusedAdamClip: step {v!r} in the optimizer state is not a step count")
+    return int(v)
+
+
+def state_to_moments(index, label, sd, exp_avg, exp_avg_sq):
+    """``torch.optim.Adam.state_dict()`` -> the flat moment buffers (everything outside the parameters -- padding, spare slots -- is
+    left zero); returns the common step count.  Saved parameter ids are mapped to positions the way ``Optimizer.load_state_dict`` does:
+    in the order the groups list them.  Everything is checked before anything is written."""
+    ids = [i for g in sd["param_groups"] for i in g["params"]]
+    if len(ids) != len(label):
+        raise ValueError(f"FusedAdamClip: the optimizer state was saved around {len(ids)} parameters, this optimizer was given {len(label)}")
+    position = {k: i for i, k in enumerate(ids)}
+    entries, steps = {}, {}
+    for k, st in sd["state"].items():
+        if k not in position:
+            raise ValueError(f"FusedAdamClip: state entry {k!r} belongs to no parameter of the saved groups")
+        i = position[k]
+        if i not in index:
+            raise ValueError(f"FusedAdamClip: the optimizer state has an entry for {label[i]!r} (params[{i}]), which is not in the flat "
+                             "buffer (frozen, or never given a gradient by the native backward)")
+        name, off, p = index[i]
+        for key in ("exp_avg", "exp_avg_sq"):
+            if tuple(st[key].shape) != tuple(p.shape):
+                raise ValueError(f"FusedAdamClip: {key} of {name!r} (params[{i}]) has shape {tuple(st[key].shape)}, the parameter "
+                                 f"{tuple(p.shape)}")
+        entries[i] = st
+        steps[i] = _step_value(st["step"])
+    if entries and len(entries) != len(index):
+        lacking = [index[i][0] for i in sorted(index) if i not in entries]
+        raise ValueError(f"FusedAdamClip: the optimizer state has entries for {len(entries)} of the {len(index)} parameters of the flat "
+                         f"buffer (none for {lacking[0]!r}): the fused pass steps all of them together")
+    if len(set(steps.values())) > 1:
+        lo, hi = min(steps, key=steps.get), max(steps, key=steps.get)
+        raise ValueError(f"FusedAdamClip: {index[lo][0]!r} is at step {steps[lo]}, {index[hi][0]!r} at step {steps[hi]}: the fused pass "
+                         "keeps one step count for all parameters")
+    if not entries:
+        exp_avg.zero_()
+        exp_avg_sq.zero_()
+        return 0
+    end = 0          # (the entries may be views of these very buffers -- load_state_dict(state_dict()) -- so only the gaps are zeroed)
+    for _, off, p in sorted(index.values(), key=lambda item: item[1]):
+        exp_avg[end:off].zero_()
+        exp_avg_sq[end:off].zero_()
+        end = off + p.numel()
+    exp_avg[end:].zero_()
+    exp_avg_sq[end:].zero_()
+    for i, st in entries.items():
+        _, off, p = index[i]
+        n = p.numel()
+        exp_avg[off:off + n].view(p.shape).copy_(st["exp_avg"])
+        exp_avg_sq[off:off + n].view(p.shape).copy_(st["exp_avg_sq"])
+    return next(iter(steps.values()))
+
+
+_ADAM_DEFAULTS = None
+
+
+def adam_group(group, num_params):
+    """a ``param_groups`` entry as ``torch.optim.Adam`` of THIS torch writes it: every key of its defaults (read from a live instance),
+    overridden by ours (``lr``, ``betas``, ``eps``, ``weight_decay``, a scheduler's ``initial_lr``, ...), over positions 0 .. n - 1"""
+    global _ADAM_DEFAULTS
+    if _ADAM_DEFAULTS is None:
+        _ADAM_DEFAULTS = dict(torch.optim.Adam([torch.nn.Parameter(torch.zeros(1))]).defaults)
+    out = dict(_ADAM_DEFAULTS)
+    out.update({k: v for k, v in group.items() if k != "params"})
+    out["params"] = list(range(num_params))
+    return out
+
+
 class FusedAdamClip(torch.optim.Optimizer):
     """A ``torch.optim.Optimizer`` (so ``torch.optim.lr_scheduler.MultiStepLR`` -- the reference's ``CFG.TRAIN.LR_SCHEDULER``,
     step/STEP_PEMS04.py:98-102 -- drives ``param_groups[0]["lr"]`` as usual) whose single parameter is the model's flat buffer."""
 
-    def __init__(self, model, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, param_grads=True):
+    def __init__(self, model, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, param_grads=True, params=None):
         """``param_grads=False`` (STEP only): the native backward leaves the gradients in the flat buffer this optimizer reads and does
-        not hand ~100 per-parameter ``.grad`` views to autograd (0.3-0.5 ms of host time per step); ``p.grad`` stays None."""
+        not hand ~100 per-parameter ``.grad`` views to autograd (0.3-0.5 ms of host time per step); ``p.grad`` stays None.
+        ``params``: the ordered sequence of Parameters whose POSITIONS are the indices of ``state_dict()`` -- what the
+        ``torch.optim.Adam`` this optimizer stands in for holds, or would hold (default: ``list(model.parameters())``).  Every
+        parameter of the flat buffer must be in it (``ValueError``); matching is by identity, which flattening keeps."""
         self.model = model
         if not param_grads and hasattr(model, "flat_gradients_only"):
             model.flat_gradients_only = True
@@ -36,6 +160,19 @@ class FusedAdamClip(torch.optim.Optimizer):
         self.grad_norm = torch.zeros(1, device=self.flat.device)
         self.dyn = None                     # device StepDynState while a GraphedTrainStep drives this optimizer
         model._backward_count = 0
+        self._bind_params(params)
+
+    def _sharded(self):
+        return getattr(getattr(self.model, "discrete_graph_learning", None), "_shard", None) is not None
+
+    def _bind_params(self, params):
+        """the identity map between positions in ``params`` and the flat buffer (not with a sharded graph learner: see state_dict)"""
+        self._index = self._label = None
+        if self._sharded():
+            return
+        params = list(self.model.parameters()) if params is None else list(params)
+        names = {id(p): n for n, p in self.model.named_parameters()}
+        self._index, self._label = index_flat_items(flat_items(self.model), params, names)
 
     def zero_grad(self, set_to_none=True):
         self.model.zero_grad(set_to_none=set_to_none)          # STEP.zero_grad also resets the flat-gradient bookkeeping
@@ -94,12 +231,31 @@ class FusedAdamClip(torch.optim.Optimizer):
                   _lib.ptr(self.grad_norm), _lib.stream())
 
     def state_dict(self):
-        groups = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
-        return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "param_groups": groups}
+        """``torch.optim.Adam``'s format over the constructor's ``params``: ``{"state": {position: {"step", "exp_avg", "exp_avg_sq"}},
+        "param_groups": [...]}``, one entry per parameter of the flat buffer (none for frozen ones, none at all before the first step).
+        The moments are views into the flat buffers, live like the tensors of torch's own ``state_dict()``: a ``torch.optim.Adam``
+        over the same parameter sequence loads the result (``copy.deepcopy`` it first if both optimizers go on stepping).
+        While a ``GraphedTrainStep`` is attached the step count is on the device: ``close()`` it first.
+        With a sharded graph learner (``discrete_graph_learning._shard``) the flat buffer holds this rank's ``fc.weight`` slice, which
+        is no parameter of torch's format: there both methods keep the flat per-rank format ``{"step", "exp_avg", "exp_avg_sq",
+        "param_groups"}`` (one file per rank)."""
+        if self._index is None:
+            groups = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
+            return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "param_groups": groups}
+        return {"state": moments_to_state(self._index, self.exp_avg, self.exp_avg_sq, self.step_count),
+                "param_groups": [adam_group(self.param_groups[0], len(self._label))]}
 
     def load_state_dict(self, sd):
-        self.step_count = sd["step"]
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        """torch's format (see ``state_dict``; ``ValueError`` for a state the fused pass cannot hold: another shape, an entry for a
+        parameter outside the flat buffer, entries for only some parameters, different step counts), or the flat format of
+        checkpoints written before (``"exp_avg"`` as a top-level key)"""
+        if "exp_avg" in sd:
+            self.step_count = _step_value(sd["step"])
+            self.exp_avg.copy_(sd["exp_avg"])
+            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        elif self._index is None:
+            raise ValueError("FusedAdamClip: with a sharded graph learner the optimizer state is the flat per-rank format, not torch's")
+        else:
+            self.step_count = state_to_moments(self._index, self._label, sd, self.exp_avg, self.exp_avg_sq)
         for g, src in zip(self.param_groups, sd["param_groups"]):
             g.update({k: v for k, v in src.items() if k != "params"})

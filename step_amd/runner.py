@@ -27,6 +27,8 @@ implementation and only changes WHERE the data lives and WHEN the host reads num
   slices where the feature list is a contiguous range (advanced indexing copies an index tensor to the device: a blocking copy).
 * ``init_training`` swaps the ``torch.optim.Adam`` + ``clip_grad_norm_`` pair the config asks for (``STEP_PEMS04.py:89-106``) for
   ``step_amd.optim.FusedAdamClip`` with the same hyper-parameters (one pass over the flat buffers); any other optimizer is left alone.
+  What easytorch's ``load_model_resume()`` restored on the replaced pair moves over (``hand_over_training_state``), and the fused
+  optimizer's ``state_dict()`` is in torch's Adam format, so checkpoints resume under either runner.
 
 The pre-training stage (``step/TSFormer_*.py``) has the same slots: ``native_runner(TSFormerRunner, native_pretrain=True)`` and
 ``CFG.DATASET_CLS = DevicePretrainingDataset`` (index-only ``(future_data, LongHistoryRef)`` batches, fused clip + Adam, loss + gradient +
@@ -245,6 +247,26 @@ class LookaheadLoader:
             yield cur
 
 
+def hand_over_training_state(old_optim, old_scheduler, new_optim, scheduler_param=None):
+    """What easytorch's ``load_model_resume()`` restored on the optimizer and the scheduler it built (moments, step counts, ``lr`` /
+    ``initial_lr``, the scheduler's ``last_epoch``) moves to the optimizer that replaces them: ``new_optim`` loads the old one's
+    ``state_dict()``, a scheduler of the old one's type is built around it from ``scheduler_param`` (``CFG.TRAIN.LR_SCHEDULER.PARAM``)
+    and loads the old scheduler's ``state_dict()``.  The scheduler's constructor takes ``initial_lr`` from the group where it finds one,
+    so its base rate is the run's, not the decayed rate of the resumed epoch.  -> the new scheduler (None without an old one).  The
+    old optimizer's state is released here: its owner drops the optimizer itself."""
+    new_optim.load_state_dict(old_optim.state_dict())
+    new = None
+    if old_scheduler is not None:
+        new = type(old_scheduler)(new_optim, **(scheduler_param or {}))
+        new.load_state_dict(old_scheduler.state_dict())
+    for old_group, group in zip(old_optim.param_groups, new_optim.param_groups):
+        for k in ("lr", "initial_lr"):          # (the scheduler's constructor takes a step of its own)
+            if k in old_group:
+                group[k] = old_group[k]
+    old_optim.state.clear()
+    return new
+
+
 class _Deferred:
     """what a metric returns while the meters are deferred: ``.item()`` hands back the device value instead of waiting for it"""
 
@@ -374,13 +396,15 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                 return
             if pretrain:
                 model.flatten_parameters()          # (values and state_dict unchanged: every parameter becomes a view into one buffer)
+            # positions in the replaced Adam's own list are the indices of the optimizer state on disk, whether easytorch handed it
+            # model.parameters() or only the trainable ones
             fused = FusedAdamClip(model, lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"],
-                                  max_norm=clip.get("max_norm"), param_grads=pretrain)
+                                  max_norm=clip.get("max_norm"), param_grads=pretrain, params=g["params"])
             sched = getattr(self, "scheduler", None)
-            if sched is not None:
-                s = cfg["TRAIN"].get("LR_SCHEDULER")
-                self.scheduler = type(sched)(fused, **s["PARAM"])
+            s = cfg["TRAIN"].get("LR_SCHEDULER") if sched is not None else None
+            self.scheduler = hand_over_training_state(opt, sched, fused, s["PARAM"] if s is not None else None)
             self.optim, self.clip_grad_param = fused, None          # the clip is part of the fused pass
+            del opt, g, sched          # the last references to the replaced Adam (its moments: two copies of the parameters)
 
         # ---------------------------------------------------------------- meters without a device synchronisation per iteration
         def train_iters(self, epoch, iter_index, data):
