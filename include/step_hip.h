@@ -168,7 +168,12 @@ typedef struct StepDglParams {
 /* Global node feature g[N,100] (discrete_graph_learning.py:131-136) from the constant train
  * series series_nt[N,T] (node-major copy of node_feats).  training!=0: batch statistics +
  * running-stat update (momentum 0.1, unbiased variance) exactly like torch.nn.BatchNorm1d.
- * saved/work: caller-owned scratch of step_dgl_global_{saved,work}_floats floats. */
+ * saved/work: caller-owned scratch of step_dgl_global_{saved,work}_floats floats; their contents on entry are arbitrary (the forward
+ * writes everything the backward reads), nothing outside those floats is touched.
+ * Shapes: any N > 0 and T > 18 (T - 18 >= 1 conv2 outputs) in both contraction modes.  p->gemm_bf16 = 1 has no lower bound of its
+ * own: its fused epilogue needs 16-byte rows and channels % 8 == 0, which the 16 bf16 channels of a conv2 row always give; the
+ * exact-f32 mode switches from the three-pass to the fused BatchNorm2 backward at T - 18 >= 128.  Only the time-sliced backward
+ * (step_dgl_global_backward_shard) needs >= 128 conv2 columns per slice and rejects less with STEP_ERR_ARG before any launch. */
 long step_dgl_global_saved_floats(int N, int T);
 long step_dgl_global_work_floats(int N, int T, int backward);
 int step_dgl_global_forward(const float* series_nt, int N, int T, const StepDglParams* p, int training,

@@ -771,12 +771,18 @@ static long fc_splitk_ws_floats(int N, int T2) {
     const int splits = step_gemm_auto_splitk(N, EMB, 16 * T2, 1);
     return splits > 1 ? (long)splits * N * EMB + 4 : 0;
 }
+// the raw fc weight gradient [EMB][16 (T-18)] of the backward's work buffer; the conv2 data gradient later keeps its packed weight
+// fragments there (dgl_conv2_pack_floats() floats, more than the gradient's 1600 at T - 18 = 1: they ran over the start of dgpre)
+static long wraw_floats(long T2) {
+    const long w = (long)EMB * 16 * T2, pack = dgl_conv2_pack_floats();
+    return w > pack ? w : pack;
+}
 extern "C" long step_dgl_global_work_floats(int N, int T, int backward) {
     long T1 = T - 9, T2 = T - 18;
     long nb1 = (long)N * cdiv(T1, 1024), nb2 = (long)N * cdiv(T2, 1024);
     long part = (nb1 > nb2 ? nb1 : nb2) * 32 + 64;
     if (!backward) return part + dgl_conv2_pack_floats() + 64 + fc_splitk_ws_floats(N, (int)T2);
-    return part + (long)N * 16 * T2 + (long)N * 8 * T1 + (long)EMB * 16 * T2 + 2L * N * EMB + DGL_SMALL + dgl_conv2_wgrad_scratch_floats(N, (int)T1);
+    return part + (long)N * 16 * T2 + (long)N * 8 * T1 + wraw_floats(T2) + 2L * N * EMB + DGL_SMALL + dgl_conv2_wgrad_scratch_floats(N, (int)T1);
 }
 
 static float* saved_wp(float* saved, int N, int T) {        // [EMB][16 (T-18)] scaled fc weight copy, then shiftdot [128]
@@ -914,7 +920,7 @@ extern "C" long step_dgl_global_offset(int N, int T, int item) {
     if (item == 1) return (long)N * 8 * T1;
     if (item == 2) return (long)N * 8 * T1 + (long)N * 16 * T2;
     const long nb1 = (long)N * cdiv(T1, 1024), nb2 = (long)N * cdiv(T2, 1024);
-    const long coef = (nb1 > nb2 ? nb1 : nb2) * 32 + 64 + (long)N * 16 * T2 + (long)N * 8 * T1 + (long)EMB * 16 * T2 + 2L * N * EMB;
+    const long coef = (nb1 > nb2 ? nb1 : nb2) * 32 + 64 + (long)N * 16 * T2 + (long)N * 8 * T1 + wraw_floats(T2) + 2L * N * EMB;
     if (item == 10) return coef + 256;
     if (item == 11) return coef + 320;
     return -1;
@@ -967,7 +973,7 @@ static int dgl_global_backward_impl(const float* series_nt, int N, int T, const 
     float* d_a2 = work + (nb1 > nb2 ? nb1 : nb2) * 32 + 64;
     float* d_a1 = d_a2 + (long)N * 16 * T2;
     float* wraw = d_a1 + (long)N * 8 * T1;
-    float* dgpre = wraw + (long)EMB * K;
+    float* dgpre = wraw + wraw_floats(T2);
     float* dgpreT = dgpre + (long)N * EMB;
     float* coef = dgpreT + (long)N * EMB;
     float* dots = coef + 256;            // written by phase 1 (dW GEMM epilogue), read by phase 2

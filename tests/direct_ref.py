@@ -1,8 +1,9 @@
-"""Direct drivers and float64 references of the GraphWaveNet backbone and of the graph learner's edge kernels.
+"""Direct drivers and float64 references of the GraphWaveNet backbone and of the graph learner's edge and global-feature kernels.
 
-Shared by tests/test_gpu_gwnet_direct.py, tests/test_gpu_dgl_edges_direct.py (device side: ``run_gwnet`` / ``run_edges`` call
-``step_gwnet_{forward,backward}`` / ``step_dgl_edges_{forward,backward}`` through ctypes, outside ``step_amd.STEP``) and
-tests/test_direct_ref_host.py (which pins ``gwnet_ref`` / ``edges_ref`` to the reference's golden numbers).  The references are
+Shared by tests/test_gpu_gwnet_direct.py, tests/test_gpu_dgl_edges_direct.py, tests/test_gpu_dgl_global_direct.py (device side:
+``run_gwnet`` / ``run_edges`` / ``run_global`` / ``run_global_sliced`` call ``step_gwnet_{forward,backward}`` /
+``step_dgl_edges_{forward,backward}`` / ``step_dgl_global_*`` through ctypes, outside ``step_amd.STEP``) and
+tests/test_direct_ref_host.py (which pins ``gwnet_ref`` / ``edges_ref`` / ``global_ref`` to the reference's golden numbers).  The references are
 ``oracle/step_oracle.py`` under autograd in the requested dtype; nothing here restates arithmetic a second time, except the bf16
 operand models: that of the diffusion hop (``_RoundedHop``), which follows ``nconv_fwd3`` / ``nconv_bwd_data3`` / the adjacency-gradient
 contraction of ``step_amd/csrc/gwnet.hip``: those three products round BOTH operands to bf16 (round to nearest even: the support
@@ -11,6 +12,8 @@ f32; what they write (the hop outputs in the gcn buffer, the gradient slots, the
 only where the next such product reads it.  ``_RoundedContractions`` extends the same treatment to the other contractions that
 ``StepGwnetParams.gemm_bf16 = 1`` moves to the bf16 matrix cores (gated TCN, skip / mix / end convolutions, fc_his): the flag switches
 them all, so a model of the hops alone is not a model of what the device computes in that mode.
+
+The global branch has its own operand model, ``global_bf16_model`` (see there).
 
 FLOOR_REL / FLOOR_ABS: the run-to-run noise of the kernels' float32 atomics, measured by test_buffers_can_be_reused (largest
 difference between two runs in fresh buffers: 1.78e-6 relative L2 on start_b, 1.71e-6 max-abs on an analytically zero gcn bias).
@@ -483,3 +486,351 @@ def cached_edge_case(B, N):
 def cached_edges_ref(B, N, dtype, variant=None):
     c = cached_edge_case(B, N)
     return edges_ref(dtype, c["ep"], c["g"], c["u"], c["dtheta"], c["dadj"], variant=variant)
+
+
+# ----------------------------------------------------------------------------------------- the graph learner's global branch
+GLOBAL_TRAINABLE = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "fc_w", "fc_b", "bn1_w", "bn1_b", "bn2_w", "bn2_b", "bn3_w", "bn3_b")
+GLOBAL_RUNNING = ("bn1_rm", "bn1_rv", "bn2_rm", "bn2_rv", "bn3_rm", "bn3_rv")
+FRESH_FC_GRAD = 16          # STEP_DGL_FRESH_FC_GRAD of include/step_hip.h
+GUARD = 4096                # floats of guard band on either side of a buffer handed to the library
+_GUARD_FRONT, _GUARD_BACK = 0x5A17C0DE, 0x3C69A5F1
+
+
+# The shapes (N, T) of tests/test_gpu_dgl_global_direct.py, each on an edge of the kernels (T2 = T - 18, T1 = T - 9): T2 = 1 (the smallest
+# the entry point accepts) and 10 (one kernel width); 127 / 128 (three-pass / fused BatchNorm2 backward in f32 mode); 132 with four row
+# tiles and a tail; 256 = WG_SC; row-tile tails of the fc GEMMs; 1024 / 1025 = FW_TT (+ 1); 3584 / 3585 = WG_SC x WG_PASSES (+ 1); the two
+# shapes of the time-slice cases.  No N below 13 (N = 5 and 7 give a dead BatchNorm3 feature: variance exactly 0).  tests/test_direct_ref_host.py
+# holds every one of them to the conditioning the tolerance rule relies on.
+GLOBAL_SHAPES = [(33, 19), (33, 28), (13, 145), (13, 146), (260, 150), (13, 274), (70, 300), (131, 300), (13, 600), (70, 600), (13, 1042),
+                 (13, 1043), (13, 3602), (13, 3603)]
+GLOBAL_FORWARD_ONLY = [(8200, 40)]          # nblk >= 8192 of dgl_bn_stats; float32 autograd on the CPU is itself 1e-3 off on its gradients
+GLOBAL_SLICED = [(13, 600, ((0, 291), (291, 582))), (13, 600, ((0, 194), (194, 388), (388, 582))), (13, 600, ((0, 200), (200, 582))),
+                 (70, 600, ((0, 291), (291, 582)))]
+# the tolerance rule's two numbers for the global branch (measured: docstring of tests/test_gpu_dgl_global_direct.py)
+GLOBAL_M, GLOBAL_FLOOR = 8.0, 3.0e-6
+
+
+def global_key(name):
+    """StepDglParams name -> state_dict key (with the prefix the oracle takes)"""
+    base, kind = name.rsplit("_", 1)
+    return EDGE_PRE + base + {"w": ".weight", "b": ".bias", "rm": ".running_mean", "rv": ".running_var"}[kind]
+
+
+def global_case(N, T, seed=0):
+    """Seeded host tensors of one call of the global branch: the series [N, T] (a daily sine with a per-node phase plus 0.3 noise, the
+    recipe of tests/test_gpu_dgl_conv.py, drawn in the same order from the same seed N * 1000 + T), the twelve trainable tensors
+    (weights scaled 0.3 / 0.1 / K ** -0.5, BatchNorm weights 0.5 + rand), dg [N, 100], and the six running statistics moved off 0 / 1:
+    started at their defaults, a swapped mean / variance or a wrong momentum would go unnoticed."""
+    gen = torch.Generator().manual_seed(N * 1000 + T + 104729 * seed)
+    tt = torch.arange(T, dtype=torch.float32)
+    series = torch.sin(2 * 3.14159265 * tt[None, :] / 288.0 + 6.28 * torch.rand(N, 1, generator=gen)) + 0.3 * torch.randn(N, T, generator=gen)
+    K = 16 * (T - 18)
+    p = {"conv1_w": torch.randn(8, 1, 10, generator=gen) * 0.3, "conv1_b": torch.randn(8, generator=gen) * 0.1,
+         "conv2_w": torch.randn(16, 8, 10, generator=gen) * 0.1, "conv2_b": torch.randn(16, generator=gen) * 0.1,
+         "fc_w": torch.randn(100, K, generator=gen) * (1.0 / K ** 0.5), "fc_b": torch.randn(100, generator=gen) * 0.1,
+         "bn1_w": torch.rand(8, generator=gen) + 0.5, "bn1_b": torch.randn(8, generator=gen) * 0.1,
+         "bn2_w": torch.rand(16, generator=gen) + 0.5, "bn2_b": torch.randn(16, generator=gen) * 0.1,
+         "bn3_w": torch.rand(100, generator=gen) + 0.5, "bn3_b": torch.randn(100, generator=gen) * 0.1}
+    dg = torch.randn(N, 100, generator=gen)
+    for name, C in (("bn1", 8), ("bn2", 16), ("bn3", 100)):
+        p[name + "_rm"] = 0.2 * torch.randn(C, generator=gen)
+        p[name + "_rv"] = 0.5 + torch.rand(C, generator=gen)
+    return {"N": N, "T": T, "series": series, "p": p, "dg": dg}
+
+
+def global_ref(dtype, case, training=True, momentum=MOMENTUM, stats_out=None):
+    """O.dgl_global_feature under autograd in ``dtype`` with loss sum(g * dg).  -> {"g" [N,100], "grads": the twelve gradients under
+    the StepDglParams names (training only), "running": the six running statistics after the call (momentum, unbiased variance;
+    unchanged in eval mode)}.  stats_out (dict): receives the oracle's batch statistics name -> (mean, unbiased variance)."""
+    p = {global_key(k): v.detach().to(dtype).clone().requires_grad_(k in GLOBAL_TRAINABLE and training) for k, v in case["p"].items()}
+    stats = {} if stats_out is None else stats_out
+    with torch.set_grad_enabled(training):
+        g = O.dgl_global_feature(case["series"].to(dtype).t(), p, EDGE_PRE, training, stats=stats)
+    out = {"g": g.detach(), "grads": {}, "running": {}}
+    if training:
+        (g * case["dg"].to(dtype)).sum().backward()
+        out["grads"] = {k: p[global_key(k)].grad for k in GLOBAL_TRAINABLE}
+    for bn in ("bn1", "bn2", "bn3"):
+        rm, rv = p[global_key(bn + "_rm")].detach(), p[global_key(bn + "_rv")].detach()
+        if training:
+            mu, var_u = stats[bn]
+            rm, rv = (1 - momentum) * rm + momentum * mu, (1 - momentum) * rv + momentum * var_u
+        out["running"][bn + "_rm"], out["running"][bn + "_rv"] = rm, rv
+    return out
+
+
+def flat_global(out):
+    """every compared tensor of a result of the global branch (device, reference or model) under one name"""
+    return {"g": out["g"], **out["grads"], **out["running"]}
+
+
+def global_bf16_model(case, rounding=True, storage="bf16", training=True, momentum=MOMENTUM):
+    """What bf16 mode (StepDglParams.gemm_bf16 = 1) computes, in float64 arithmetic with a round-to-nearest-even bf16 exactly where
+    the device rounds -- the forward and the hand-written backward of step_amd/csrc/dgl.hip / dgl_conv_mfma.hip / the fused epilogues
+    of gemm_bf16.hip, step by step (this is not autograd of a rounded forward: the device's backward is not that either).  With
+    rounding off it is the oracle's function and gradient (tests/test_direct_ref_host.py holds it to global_ref(float64) at 1e-12).
+
+    storage = "bf16" (the default of the mode: channels-last bf16 rows):
+      conv1 is f32 arithmetic; its output is STORED rounded (a1), BatchNorm1's sums are taken from the f32 values before that rounding
+      (conv1_fwd_cl_kernel).  conv2 multiplies the stored rows by bf16(w * scale1) and adds the folded bias in f32 (conv2_pack_kernel);
+      BatchNorm2's sums again come from the f32 values, the output is stored rounded (a2).  The fc multiplies a2 by
+      bf16(fc_w * scale2) and starts from the f32 shift term (fc_prep_kernel).  Backward: BatchNorm3 / ReLU in f32; G = bf16(dgpre)^T a2,
+      un-permuted with BatchNorm2's affine in f32, BatchNorm2's two sums from fc_w . G and fc_w . colsum in f32 (fc_unpermute_kernel);
+      dz2 = the BatchNorm2 backward transform of bf16(dgpre) bf16(fc_w * scale2) with x = the stored a2, stored rounded (the
+      GEMM_FUSED_INTERLEAVED epilogue); the conv2 weight-gradient sums and the conv2 bias gradient from the STORED dz2 and a1
+      (conv2_wgrad_cl_kernel), normalised afterwards (conv2_wgrad_finish_kernel, raw = 1); dz1 from the stored dz2, bf16(w * scale1)
+      and the stored a1, stored rounded (conv2_dgrad_cl_kernel); conv1's gradients from the stored dz1 and bf16(series).
+    storage = "f32" (STEP_DGL_F32_STORAGE=1, with the fused BatchNorm backward: T - 18 >= 128): the activations and their gradients
+      stay f32 and every product rounds its two operands as it reads them: conv2 bf16(scale1 a1 + shift1) bf16(w); the fc
+      bf16(scale2 a2 + shift2) bf16(fc_w); dz2 from bf16(dgpre) bf16(fc_w) with the transform in f32; the conv2 weight gradient
+      bf16(dz2) bf16(xhat1) with the bias gradient from the f32 dz2; dz1 from bf16(dz2) bf16(w); conv1's from bf16(dz1) bf16(series)."""
+    assert storage in ("bf16", "f32")
+    F = torch.nn.functional
+    R = round_bf16 if rounding else (lambda t: t)
+    cl = storage == "bf16"
+    f64 = torch.float64
+    P = {k: v.detach().to(f64) for k, v in case["p"].items()}
+    x, dg = case["series"].to(f64), case["dg"].to(f64)
+    N, T = x.shape
+    T1, T2 = T - 9, T - 18
+    assert cl or T2 >= 128 or not training
+    eps = O.BN_EPS
+    ch = lambda v: v.view(1, -1, 1)
+    W1, W2, Wf = P["conv1_w"], P["conv2_w"], P["fc_w"].view(100, 16, T2)
+    running = {}
+
+    def statistics(a, dims, name):          # mean, 1 / sqrt(var + eps) of the values BEFORE any rounding
+        if training:
+            n = a.numel() // a.shape[1]
+            mu = a.mean(dims)
+            var = ((a - (ch(mu) if a.dim() == 3 else mu)) ** 2).mean(dims)
+            running[name + "_rm"] = (1 - momentum) * P[name + "_rm"] + momentum * mu
+            running[name + "_rv"] = (1 - momentum) * P[name + "_rv"] + momentum * var * (n / max(n - 1, 1))
+        else:
+            mu, var = P[name + "_rm"], P[name + "_rv"]
+            running[name + "_rm"], running[name + "_rv"] = mu, var
+        return mu, (var + eps).rsqrt()
+
+    # ---- forward
+    c1 = torch.relu(F.conv1d(x.unsqueeze(1), W1, P["conv1_b"]))
+    mu1, rstd1 = statistics(c1, (0, 2), "bn1")
+    sc1 = P["bn1_w"] * rstd1
+    sh1 = P["bn1_b"] - mu1 * sc1
+    if cl:
+        a1, w2f = R(c1), R(W2 * ch(sc1))
+        c2 = torch.relu(F.conv1d(a1, w2f, P["conv2_b"] + (W2.sum(2) * sh1).sum(1)))
+    else:
+        a1 = c1
+        c2 = torch.relu(F.conv1d(R(c1 * ch(sc1) + ch(sh1)), R(W2), P["conv2_b"]))
+    mu2, rstd2 = statistics(c2, (0, 2), "bn2")
+    sc2 = P["bn2_w"] * rstd2
+    sh2 = P["bn2_b"] - mu2 * sc2
+    a2 = R(c2)                                    # what the fc weight gradient reads in either storage
+    if cl:
+        wp = R(Wf * ch(sc2))
+        gpre = torch.einsum("nct,oct->no", a2, wp) + (Wf * ch(sh2)).sum((1, 2)) + P["fc_b"]
+    else:
+        gpre = torch.einsum("nct,oct->no", R(c2 * ch(sc2) + ch(sh2)), R(Wf)) + P["fc_b"]
+    r3 = torch.relu(gpre)
+    mu3, rstd3 = statistics(r3, (0,), "bn3")
+    out = {"g": (r3 - mu3) * rstd3 * P["bn3_w"] + P["bn3_b"], "grads": {}, "running": running}
+    if not training:
+        return out
+
+    # ---- backward
+    gr = out["grads"]
+    xh3 = (r3 - mu3) * rstd3
+    S1, S2 = dg.sum(0), (dg * xh3).sum(0)
+    gr["bn3_w"], gr["bn3_b"] = S2, S1
+    dgpre = torch.where(gpre > 0, P["bn3_w"] * rstd3 * (dg - S1 / N - xh3 * S2 / N), torch.zeros_like(dg))
+    colsum = dgpre.sum(0)
+    gr["fc_b"] = colsum
+    G = torch.einsum("no,nct->oct", R(dgpre), a2)
+    gr["fc_w"] = (ch(sc2) * G + ch(sh2) * colsum.view(-1, 1, 1)).reshape(100, -1)
+    S1 = torch.einsum("oct,o->c", Wf, colsum)
+    S2 = rstd2 * ((Wf * G).sum((0, 2)) - mu2 * S1)
+    gr["bn2_w"], gr["bn2_b"] = S2, S1
+    m1, m2, kc = S1 / (N * T2), S2 / (N * T2), P["bn2_w"] * rstd2
+    if cl:
+        v = torch.einsum("no,oct->nct", R(dgpre), wp)
+        dz2 = R(torch.where(a2 > 0, v - ch(kc * m1) - (a2 - ch(mu2)) * ch(kc * m2 * rstd2), torch.zeros_like(v)))
+        dz2_op = dz2
+    else:
+        v = torch.einsum("no,oct->nct", R(dgpre), R(Wf))
+        dz2 = torch.where(c2 > 0, ch(kc) * (v - ch(m1) - (c2 - ch(mu2)) * ch(m2 * rstd2)), torch.zeros_like(v))
+        dz2_op = R(dz2)
+    db2 = dz2.sum((0, 2))
+    corr = lambda inp, dz: F.conv1d(inp.transpose(0, 1), dz.transpose(0, 1)).transpose(0, 1)          # [co, ci, kk] = sum_{n,t} dz[n,co,t] inp[n,ci,t+kk]
+    if cl:
+        Gp = ch(rstd1) * (corr(a1, dz2_op) - ch(mu1) * db2.view(-1, 1, 1))
+    else:
+        Gp = corr(R((c1 - ch(mu1)) * ch(rstd1)), dz2_op)
+    gr["conv2_w"] = ch(P["bn1_w"]) * Gp + ch(P["bn1_b"]) * db2.view(-1, 1, 1)
+    gr["conv2_b"] = db2
+    S1 = (W2.sum(2) * db2.view(-1, 1)).sum(0)
+    S2 = (W2 * Gp).sum((0, 2))
+    gr["bn1_w"], gr["bn1_b"] = S2, S1
+    m1, m2, kc = S1 / (N * T1), S2 / (N * T1), P["bn1_w"] * rstd1
+    if cl:
+        d_a1 = F.conv_transpose1d(dz2_op, w2f)
+        dz1 = R(torch.where(a1 > 0, d_a1 - ch(kc * m1) - (a1 - ch(mu1)) * ch(kc * m2 * rstd1), torch.zeros_like(d_a1)))
+        dz1_op = dz1
+    else:
+        d_a1 = F.conv_transpose1d(dz2_op, R(W2))
+        dz1 = torch.where(c1 > 0, ch(kc) * (d_a1 - ch(m1) - (c1 - ch(mu1)) * ch(m2 * rstd1)), torch.zeros_like(d_a1))
+        dz1_op = R(dz1)
+    gr["conv1_w"] = F.conv1d(R(x).unsqueeze(0), dz1_op.transpose(0, 1)).view(8, 1, 10)
+    gr["conv1_b"] = dz1.sum((0, 2))
+    return out
+
+
+class _Guarded:
+    """n floats for the library between two guard bands of GUARD floats each (a fixed bit pattern in front, another one behind); the
+    library is handed exactly the n floats in the middle, which start as NaN bytes"""
+
+    def __init__(self, n, dev):
+        self.n = int(n)
+        self.raw = torch.empty(self.n + 2 * GUARD, dtype=torch.int32, device=dev)
+        self.raw[:GUARD] = _GUARD_FRONT
+        self.raw[GUARD + self.n:] = _GUARD_BACK
+        self.raw[GUARD:GUARD + self.n] = -1
+        self.t = self.raw[GUARD:GUARD + self.n].view(torch.float32)
+
+    def intact(self):
+        return bool((self.raw[:GUARD] == _GUARD_FRONT).all()) and bool((self.raw[GUARD + self.n:] == _GUARD_BACK).all())
+
+
+def _global_buffers(lib, N, T, dev):
+    return (_Guarded(lib.step_dgl_global_saved_floats(N, T), dev), _Guarded(lib.step_dgl_global_work_floats(N, T, 0), dev),
+            _Guarded(lib.step_dgl_global_work_floats(N, T, 1), dev))
+
+
+def run_global(case, bf16=0, training=1, momentum=MOMENTUM, grad_fill=None, phases=(0,), fresh_fc=False, buffers=None, backward=True):
+    """step_dgl_global_forward + step_dgl_global_backward_phase (once per entry of ``phases``, in the same work buffer) through ctypes.
+    saved / work / g and, with fresh_fc, grads.fc_w start as NaN bytes; saved and both work buffers hold exactly
+    step_dgl_global_{saved,work}_floats floats between two guard bands.  grad_fill: name -> G0 the gradient buffers start from (None:
+    zeros).  buffers: those of an earlier call, to run in again (not refilled).  -> host copies: g, grads (after the last phase),
+    grads_after (one dict per phase), running / initial (the six statistics after / before), guards_intact, buffers."""
+    from step_amd import _lib as L
+    from step_amd.step_arch.discrete_graph_learning import fill_dgl_struct
+    dev = torch.device("cuda")
+    N, T = case["N"], case["T"]
+    lib = L.lib()
+    series = case["series"].to(dev).contiguous()
+    params = {k: v.to(dev).contiguous().clone() for k, v in case["p"].items()}
+    struct = fill_dgl_struct(params, bf16)
+    if buffers is None:
+        buffers = _global_buffers(lib, N, T, dev)
+    saved, wfwd, wbwd = buffers
+    g = _nan_floats(N * 100, dev).view(N, 100)
+    initial = {k: params[k].cpu() for k in GLOBAL_RUNNING}
+    st = L.stream()
+    L.call("step_dgl_global_forward", L.ptr(series), N, T, ctypes.byref(struct), int(training), float(momentum), L.ptr(saved.t), L.ptr(wfwd.t),
+           L.ptr(g), st)
+    torch.cuda.synchronize()
+    out = {"g": g.cpu(), "grads": {}, "grads_after": [], "running": {k: params[k].cpu() for k in GLOBAL_RUNNING}, "initial": initial,
+           "buffers": buffers}
+    if training and backward:
+        dg = case["dg"].to(dev).contiguous()
+        grads = {k: (torch.zeros_like(params[k]) if grad_fill is None else grad_fill[k].to(dev).contiguous().clone()) for k in GLOBAL_TRAINABLE}
+        if fresh_fc:
+            grads["fc_w"] = _nan_floats(params["fc_w"].numel(), dev).view_as(params["fc_w"])
+        gstruct = fill_dgl_struct(grads, bf16)
+        for ph in phases:
+            L.call("step_dgl_global_backward_phase", L.ptr(series), N, T, ctypes.byref(struct), L.ptr(saved.t), L.ptr(dg), L.ptr(wbwd.t),
+                   ctypes.byref(gstruct), int(ph) | (FRESH_FC_GRAD if fresh_fc else 0), st)
+            torch.cuda.synchronize()
+            out["grads_after"].append({k: v.cpu() for k, v in grads.items()})
+        out["grads"] = out["grads_after"][-1]
+    out["guards_intact"] = all(b.intact() for b in buffers)
+    return out
+
+
+def run_global_sliced(case, bounds):
+    """The time-sliced entry points step_dgl_global_{forward,backward}_shard in ONE process, without a communicator: this driver is the
+    caller of include/step_hip.h.  bounds: [(a, b)] column ranges of the T - 18 conv2 outputs; every slice has its own saved / work
+    (guarded, NaN-filled), the series columns [a, b + 18) and the weight columns fc.weight.view(100, 16, T - 18)[:, :, a:b].  Between
+    the calls the driver sums over the slices, with torch on the one stream: `sums` [0,16) after forward phase 1 and [16,48) after
+    phase 2, gpre after phase 3; the 32 dots (offset item 10) after backward phase 1 and the 1296 graw values (item 11) after phase 3.
+    own1 = b - a (+ 9 on the last slice), count1 / count2 = N (T - 9) / N (T - 18) of the whole series.  bf16 mode, fc_w stored
+    (STEP_DGL_FRESH_FC_GRAD, as step.py calls it) into NaN bytes.  -> g (asserted identical on every slice), the fc weight gradient
+    reassembled from the slices, the conv1 gradients summed over them, the rest from slice 0; running / initial of slice 0."""
+    from step_amd import _lib as L
+    from step_amd.step_arch.discrete_graph_learning import fill_dgl_struct
+    dev = torch.device("cuda")
+    N, T = case["N"], case["T"]
+    T2 = T - 18
+    lib = L.lib()
+    st = L.stream()
+    dg = case["dg"].to(dev).contiguous()
+    assert bounds[0][0] == 0 and bounds[-1][1] == T2 and all(bounds[i][1] == bounds[i + 1][0] for i in range(len(bounds) - 1))
+    sl = []
+    for i, (a, b) in enumerate(bounds):
+        s = {"a": a, "b": b, "Ts": b - a + 18}
+        s["series"] = case["series"][:, a:b + 18].contiguous().to(dev)
+        s["params"] = {k: v.to(dev).contiguous().clone() for k, v in case["p"].items() if k != "fc_w"}
+        s["params"]["fc_w"] = case["p"]["fc_w"].view(100, 16, T2)[:, :, a:b].contiguous().view(100, -1).to(dev)
+        s["struct"] = fill_dgl_struct(s["params"], 1)
+        s["shard"] = L.StepDglShard()
+        s["shard"].own1, s["shard"].count1, s["shard"].count2 = (b - a) + (9 if i == len(bounds) - 1 else 0), float(N) * (T - 9), float(N) * T2
+        s["buffers"] = _global_buffers(lib, N, s["Ts"], dev)
+        s["sums"] = torch.zeros(48, dtype=torch.float64, device=dev)
+        s["g"] = _nan_floats(N * 100, dev).view(N, 100)
+        go = lib.step_dgl_global_offset(N, s["Ts"], 2)
+        s["gpre"] = s["buffers"][0].t[go:go + N * 100]
+        o_dots, o_graw = lib.step_dgl_global_offset(N, s["Ts"], 10), lib.step_dgl_global_offset(N, s["Ts"], 11)
+        assert go >= 0 and o_dots >= 0 and o_graw + 1296 <= s["buffers"][2].n
+        s["dots"], s["graw"] = s["buffers"][2].t[o_dots:o_dots + 32], s["buffers"][2].t[o_graw:o_graw + 1296]
+        s["grads"] = {k: torch.zeros_like(v) for k, v in s["params"].items() if k in GLOBAL_TRAINABLE and k != "fc_w"}
+        s["grads"]["fc_w"] = _nan_floats(s["params"]["fc_w"].numel(), dev).view_as(s["params"]["fc_w"])
+        s["gstruct"] = fill_dgl_struct(s["grads"], 1)
+        sl.append(s)
+    initial = {k: sl[0]["params"][k].cpu() for k in GLOBAL_RUNNING}
+
+    def sum_over_slices(views):
+        total = torch.stack(views).sum(0)
+        for v in views:
+            v.copy_(total)
+
+    for phase in (1, 2, 3, 4):
+        for s in sl:
+            L.call("step_dgl_global_forward_shard", L.ptr(s["series"]), N, s["Ts"], ctypes.byref(s["struct"]), 1, MOMENTUM, L.ptr(s["buffers"][0].t),
+                   L.ptr(s["buffers"][1].t), L.ptr(s["sums"]), L.ptr(s["g"]), ctypes.byref(s["shard"]), phase, st)
+        if phase == 1:
+            sum_over_slices([s["sums"][:16] for s in sl])
+        elif phase == 2:
+            sum_over_slices([s["sums"][16:] for s in sl])
+        elif phase == 3:
+            sum_over_slices([s["gpre"] for s in sl])
+    for phase in (1, 3, 4):
+        for s in sl:
+            L.call("step_dgl_global_backward_shard", L.ptr(s["series"]), N, s["Ts"], ctypes.byref(s["struct"]), L.ptr(s["buffers"][0].t), L.ptr(dg),
+                   L.ptr(s["buffers"][2].t), ctypes.byref(s["gstruct"]), ctypes.byref(s["shard"]), phase | FRESH_FC_GRAD, st)
+        if phase == 1:
+            sum_over_slices([s["dots"] for s in sl])
+        elif phase == 3:
+            sum_over_slices([s["graw"] for s in sl])
+    torch.cuda.synchronize()
+    for s in sl[1:]:
+        assert torch.equal(s["g"], sl[0]["g"]), "g differs between the slices"
+    grads = {k: v.cpu() for k, v in sl[0]["grads"].items()}
+    grads["fc_w"] = torch.cat([s["grads"]["fc_w"].view(100, 16, -1) for s in sl], dim=2).reshape(100, -1).cpu()
+    for k in ("conv1_w", "conv1_b"):
+        grads[k] = torch.stack([s["grads"][k] for s in sl]).sum(0).cpu()
+    return {"g": sl[0]["g"].cpu(), "grads": grads, "running": {k: sl[0]["params"][k].cpu() for k in GLOBAL_RUNNING}, "initial": initial,
+            "guards_intact": all(b.intact() for s in sl for b in s["buffers"])}
+
+
+@functools.lru_cache(maxsize=None)
+def cached_global_case(N, T):
+    return global_case(N, T)
+
+
+@functools.lru_cache(maxsize=None)
+def cached_global_ref(N, T, dtype, training=True, momentum=MOMENTUM):
+    return global_ref(dtype, cached_global_case(N, T), training=training, momentum=momentum)
+
+
+@functools.lru_cache(maxsize=None)
+def cached_global_model(N, T, storage="bf16", training=True):
+    return global_bf16_model(cached_global_case(N, T), storage=storage, training=training)

@@ -257,6 +257,21 @@ def test_workspace_size_queries_are_pure_host_functions():
     assert lib.step_adam_work_floats() > 0
 
 
+def test_global_work_buffer_holds_the_packed_conv2_weights_at_the_smallest_shape():
+    """The backward of the graph learner's global branch keeps the conv2 data gradient's packed weight fragments (8 x 64 x 16 bytes +
+    16 floats = 2064 floats) in the region of the raw fc weight gradient (100 x 16 (T - 18) floats), which is spent by then.  At
+    T - 18 = 1 that gradient has only 1600 floats: the region is sized for the larger of the two, and step_dgl_global_offset follows."""
+    from step_amd import _lib
+    lib = _lib.lib()
+    pack = 8 * 64 * 4 + 16
+    for N, T in ((1, 19), (33, 19), (13, 20), (13, 146), (307, 300)):
+        T1, T2 = T - 9, T - 18
+        part = N * max(-(-T1 // 1024), -(-T2 // 1024)) * 32 + 64
+        region = lib.step_dgl_global_offset(N, T, 10) - 256 - 2 * N * 100 - N * 8 * T1 - N * 16 * T2 - part
+        assert region == max(1600 * T2, pack), (N, T, region)
+        assert lib.step_dgl_global_offset(N, T, 11) == lib.step_dgl_global_offset(N, T, 10) + 64
+        assert lib.step_dgl_global_offset(N, T, 11) + 1296 <= lib.step_dgl_global_work_floats(N, T, 1)
+
 def test_mask_generator_seeded_matches_reference():
     """T3 (tsformer/mask.py:15-28): python random.shuffle of range(P), first 75 % masked, both lists sorted.  The golden
     lists were drawn by the reference's MaskGenerator after random.seed(4) (tools/make_golden.py run_pretrain_case)."""

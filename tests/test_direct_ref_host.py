@@ -1,8 +1,10 @@
 """Pin the float64 helper of the direct kernel tests (tests/direct_ref.py) to the reference's own numbers (tests/golden/*.npz).
 
-The direct GPU tests measure the kernels against ``gwnet_ref(float64)`` / ``edges_ref(float64)``; here those two are fed the golden
-inputs and must land on the golden outputs, so a mistake in the helper (a transposed prediction, a mis-keyed parameter, the noise eps
-added in the wrong precision) cannot pass as a kernel error or hide one.  No GPU."""
+The direct GPU tests measure the kernels against ``gwnet_ref(float64)`` / ``edges_ref(float64)`` / ``global_ref(float64)``; here those are
+fed the golden inputs and must land on the golden outputs, so a mistake in the helper (a transposed prediction, a mis-keyed parameter,
+the noise eps added in the wrong precision) cannot pass as a kernel error or hide one.  The bf16 operand model of the global branch
+is held to ``global_ref`` with its rounding switched off, and the inputs of every shape of tests/test_gpu_dgl_global_direct.py to the
+conditioning its tolerance rule relies on.  No GPU."""
 import pytest
 import torch
 
@@ -24,7 +26,11 @@ def golden(request):
                                                params_of(g32, requires_grad=False), g32["in.u"], k, epoch if epoch >= 0 else None,
                                                training=bool(training), aux=aux)
         p64 = params_of(g64, requires_grad=False)
-        gfeat = O.dgl_global_feature(g64["in.node_feats"], p64, PRE, bool(training))
+    # the global feature through global_ref's forward (StepDglParams names -> state_dict keys): a mis-keyed parameter there would move
+    # theta off the golden below
+    gcase = {"series": g64["in.node_feats"].t(), "dg": torch.zeros(N, 100, dtype=torch.float64),
+             "p": {k: p64[D.global_key(k)] for k in D.GLOBAL_TRAINABLE + D.GLOBAL_RUNNING}}
+    gfeat = D.global_ref(torch.float64, gcase, training=bool(training))["g"]
     ep = {"fc_out_w": p64[PRE + "fc_out.weight"], "fc_out_b": p64[PRE + "fc_out.bias"], "fc_cat_w": p64[PRE + "fc_cat.weight"],
           "fc_cat_b": p64[PRE + "fc_cat.bias"]}
     e64 = D.edges_ref(torch.float64, ep, gfeat, g32["in.u"])
@@ -99,3 +105,56 @@ def test_native_key_covers_the_state_dict():
     assert {k for k in sd if sd[k].is_floating_point() and not k.startswith("residual_convs.")} == keys
     for i in range(8):          # the BatchNorm tensors are off their defaults
         assert float((sd[f"bn.{i}.weight"] - 1).abs().min()) > 0 and float(sd[f"bn.{i}.running_mean"].abs().min()) > 0
+
+
+# ----------------------------------------------------------------------------------------- the graph learner's global branch
+def test_global_model_without_rounding_is_the_plain_path():
+    for (N, T), storages in (((13, 40), ("bf16",)), ((13, 160), ("bf16", "f32"))):
+        c = D.global_case(N, T, seed=3)
+        a = D.flat_global(D.global_ref(torch.float64, c))
+        assert len(a) == 19
+        for storage in storages:
+            b = D.flat_global(D.global_bf16_model(c, rounding=False, storage=storage))
+            assert set(a) == set(b)
+            for k in a:
+                assert tuple(b[k].shape) == tuple(a[k].shape), k
+                assert max_abs(b[k], a[k]) <= 1e-12 * max(1.0, float(a[k].abs().max())), (storage, k)
+            # with rounding on it is another computation of the same function: bf16 operands cost 2^-9 per product, far above 1e-12 and
+            # far below the values themselves
+            r = D.flat_global(D.global_bf16_model(c, storage=storage))
+            for k in ("g", "fc_w"):
+                assert 1e-4 < rel_l2(r[k], a[k]) < 0.25, (storage, k, rel_l2(r[k], a[k]))
+        e = D.global_ref(torch.float64, c, training=False)
+        m = D.global_bf16_model(c, rounding=False, training=False)
+        assert max_abs(m["g"], e["g"]) <= 1e-12 * max(1.0, float(e["g"].abs().max()))
+        for k in D.GLOBAL_RUNNING:          # eval mode leaves the statistics alone, in the reference and in the model
+            assert torch.equal(e["running"][k], c["p"][k].double()) and torch.equal(m["running"][k], c["p"][k].double()), k
+
+
+def test_global_case_moves_the_running_statistics_off_their_defaults():
+    c = D.global_case(13, 40)
+    for k in D.GLOBAL_RUNNING:
+        assert float((c["p"][k] - (1.0 if k.endswith("_rv") else 0.0)).abs().min()) > 0, k
+    assert set(c["p"]) == set(D.GLOBAL_TRAINABLE + D.GLOBAL_RUNNING)
+    assert torch.equal(D.global_case(13, 40)["series"], c["series"]) and not torch.equal(D.global_case(13, 40, seed=1)["series"], c["series"])
+
+
+@pytest.mark.parametrize("N,T", D.GLOBAL_SHAPES + D.GLOBAL_FORWARD_ONLY)
+def test_global_cases_are_well_conditioned(N, T):
+    """Conditions on the INPUTS of the direct GPU tests, not measurements of anything: (1) no BatchNorm channel with a batch variance
+    below 1e-3 (a dead ReLU channel divides by sqrt(eps)), (2) the float32 oracle within 2e-5 relative L2 of float64 on every compared
+    tensor (an ill-conditioned sum would hide a kernel error inside M * e_f32), and with them (3) the bound M * e_f32 + FLOOR of every
+    tensor at or below 1e-4, the tightest fixed bound the rule supersedes."""
+    stats = {}
+    r64, r32 = D.cached_global_ref(N, T, torch.float64), D.cached_global_ref(N, T, torch.float32)
+    D.global_ref(torch.float64, D.cached_global_case(N, T), stats_out=stats)
+    count = {"bn1": N * (T - 9), "bn2": N * (T - 18), "bn3": N}
+    smallest = min(float((var_u * (count[k] - 1) / count[k]).min()) for k, (_, var_u) in stats.items())
+    f64, f32 = D.flat_global(r64), D.flat_global(r32)
+    forward_only = (N, T) in D.GLOBAL_FORWARD_ONLY
+    errs = {k: rel_l2(f32[k], f64[k]) for k in f64 if not (forward_only and k in D.GLOBAL_TRAINABLE)}
+    worst = max(errs, key=errs.get)
+    print(f"N={N} T={T}: smallest batch variance {smallest:.2e}, largest e_f32 {errs[worst]:.2e} ({worst})")
+    assert smallest >= 1e-3
+    assert errs[worst] <= 2e-5, (worst, errs[worst])
+    assert D.GLOBAL_M * errs[worst] + D.GLOBAL_FLOOR <= 1e-4, (worst, errs[worst])
