@@ -601,6 +601,19 @@ long step_pretrain_tail_work_doubles(void);          /* pure host function */
 int step_pretrain_tail(const float* r, const float* series, const int* mk, int S, int P, int Pm, float scale, float shift, float null_val,
                        double* work, float* loss, float* metrics, float* dr, void* stream);
 
+/* ---------------------------------------------------------------- replica digest ----------
+ * A position-dependent 128-bit digest of a flat f32 buffer (the parameters of a data-parallel replica), so that the ranks can compare
+ * their replicas with one 32-byte collective.  It stands in for the guarantee the reference gets from DistributedDataParallel -- easytorch
+ * wraps the model when CFG.GPU_NUM > 1 (step/STEP_PEMS04.py:30, step/TSFormer_PEMS04.py), the wrapper broadcasts rank 0's state and every
+ * rank applies the same reduced gradient -- where the native data-parallel step has no wrapper (additive to ABI 10).
+ *  flat   f32 [n] on the device, 4-byte aligned (any offset into a buffer); 0 < n < 2^32
+ *  out2   two 64-bit words on the device, 8-byte aligned; cleared by the call in stream order, whatever they held
+ * Element i with bit pattern b contributes m = mix64(((uint64)i << 32) | b), mix64 the finaliser of splitmix64
+ * (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31).  out2[0] = sum of all m mod 2^64,
+ * out2[1] = xor of all m: exact and commutative, hence the same for every launch shape and alignment.  -0.0 / +0.0 and NaN payloads
+ * are told apart (bit patterns, not values). */
+int step_replica_digest(const float* flat, long n, unsigned long long* out2, void* stream);
+
 /* ---------------------------------------------------------------- self test --------------
  * Verifies on the device the MFMA operand/accumulator lane maps this library is built on
  * (cdna_hip_programming.md section 3).  out: int32[8] failure counters, all zero when ok. */

@@ -172,6 +172,8 @@ _SIGS = {
     # loss, gradient and meters of a pre-training iteration from the decoder's output and the packed series (csrc/pretrain_tail.hip)
     "step_pretrain_tail_work_doubles": (_l, []),
     "step_pretrain_tail": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
+    # 128-bit digest of a flat parameter buffer: the replica check of data-parallel training (csrc/replica_digest.hip)
+    "step_replica_digest": (_i, [_vp, _l, _vp, _vp]),
 }
 
 _lib = None

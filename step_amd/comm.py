@@ -9,6 +9,10 @@ on one rank (profiles/r04_b_C2_rccl1_noshard_timeline.md).
 
 The reference gets its data parallelism from easytorch wrapping the model in `DistributedDataParallel` (GPU_NUM > 1:
 step/STEP_PEMS04.py:30, step/STEP_PEMS07.py:29,83,117); this is the same exchange -- one mean all-reduce of the gradients per step.
+
+Also here: ``open_transport`` (which of the two transports a module's collectives take, agreed by all ranks; shared by ``STEP`` and the
+pre-training ``TSFormer``) and the replica check that stands in for DDP's guarantee of identical replicas -- ``replica_digest`` (csrc/
+replica_digest.hip: 128 bits of a flat parameter buffer, read once) and ``replicas_identical`` (one 32-byte collective over them).
 """
 import ctypes
 
@@ -20,6 +24,96 @@ from . import _lib
 def available():
     """librccl can be loaded into this process (the copy torch has already loaded, when there is one)"""
     return bool(_lib.lib().step_comm_available())
+
+
+def open_transport(process_group, collectives, device, min_world=1):
+    """The transport of a module's data-parallel collectives, agreed by all ranks of ``process_group``: -> a ``NativeComm`` (RCCL's C
+    API), or None for ``torch.distributed``.  ``collectives``: "rccl", "torch" or "auto" -- "rccl" when the group's backend is nccl
+    (= RCCL) and ``device`` is a GPU, else "torch".  "auto" promises a working data-parallel step, not a particular transport: when
+    librccl cannot be loaded or the communicator cannot be created on ANY rank it warns and every rank stays on torch.distributed
+    (two MIN all-reduces: one before anyone enters the communicator's rendezvous, one after).  An explicit "rccl" raises instead.
+    A group of ``min_world`` ranks or fewer gets no communicator (1: a single rank issues nothing; 0: it issues everything).
+    Shared by ``STEP.enable_native_data_parallel`` and ``TSFormer.enable_native_data_parallel``."""
+    import torch.distributed as dist
+    on_gpu = device.type == "cuda"
+    auto = collectives == "auto"
+    if auto:
+        collectives = "rccl" if (on_gpu and dist.get_backend(process_group) == "nccl") else "torch"
+    if collectives not in ("rccl", "torch"):
+        raise ValueError(f"collectives = {collectives!r}: expected 'auto', 'rccl' or 'torch'")
+    comm = None
+    if collectives == "rccl" and dist.get_world_size(process_group) > min_world:
+        if not on_gpu:
+            raise RuntimeError("collectives='rccl' needs the module on a GPU (move it first)")
+        if not available() and not auto:
+            raise RuntimeError("collectives='rccl': librccl could not be loaded into this process (STEP_RCCL_LIB names another copy)")
+        usable = available()
+        if auto and dist.get_world_size(process_group) > 1:
+            # agree BEFORE anyone enters ncclCommInitRank: a rank whose librccl did not load would otherwise go on to the all-reduce
+            # below while the others block in the communicator's rendezvous
+            have = torch.tensor([1 if usable else 0], device=device, dtype=torch.int32)
+            dist.all_reduce(have, op=dist.ReduceOp.MIN, group=process_group)
+            usable = bool(int(have.item()))
+        try:
+            if not usable:
+                raise RuntimeError("librccl could not be loaded on every rank")
+            comm = NativeComm(process_group)
+        except Exception as ex:          # noqa: BLE001
+            if not auto:
+                raise
+            # "auto" promised a working data-parallel step, not a particular transport: say so and stay on torch.distributed
+            import warnings
+            warnings.warn(f"step_amd: RCCL C-API communicator could not be created ({ex}); the step's collectives stay on torch.distributed")
+            comm = None
+        if auto and dist.get_world_size(process_group) > 1:
+            # all ranks take the same transport: one rank without a communicator puts every rank on torch.distributed
+            ok = torch.tensor([1 if comm is not None else 0], device=device, dtype=torch.int32)
+            dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=process_group)
+            if int(ok.item()) == 0 and comm is not None:
+                comm.close()
+                comm = None
+    return comm
+
+
+def broadcast_module_states(module, process_group):
+    """what DistributedDataParallel does when it wraps a module: every rank starts from rank 0's parameters and buffers"""
+    import torch.distributed as dist
+    src = dist.get_global_rank(process_group, 0)
+    with torch.no_grad():
+        for t in list(module.parameters()) + list(module.buffers()):
+            d = t.detach()
+            if d.is_contiguous():
+                dist.broadcast(d, src, group=process_group)
+            else:
+                c = d.contiguous()
+                dist.broadcast(c, src, group=process_group)
+                d.copy_(c)
+
+
+def replica_digest(flat):
+    """-> int64 ``[2]`` on ``flat``'s device: the two 64-bit words of ``step_replica_digest`` (the sum mod 2^64 and the xor of one
+    splitmix64-mixed word per element and position; uint64 bit patterns, exposed as int64 since torch has no uint64 arithmetic).
+    ``flat``: a contiguous f32 device tensor of fewer than 2^32 elements, at any 4-byte offset.  Nothing is read back."""
+    if not (torch.is_tensor(flat) and flat.is_cuda and flat.dtype == torch.float32 and flat.is_contiguous()):
+        raise ValueError("replica_digest: a contiguous float32 device tensor is needed")
+    out = torch.empty(2, dtype=torch.int64, device=flat.device)
+    _lib.call("step_replica_digest", _lib.ptr(flat), flat.numel(), _lib.ptr(out), _lib.stream())
+    return out
+
+
+def replicas_identical(flat, process_group=None):
+    """True when every rank of ``process_group`` holds the same bits in ``flat`` (same length on every rank): the group's MAX and MIN
+    of the digest's two words from ONE 32-byte all-reduce -- the words and their complements under MAX, since max(~x) = ~min(x) in
+    int64 order -- and one read-back.  Every rank sees the same four words, so every rank gets the same answer.  A collective: all
+    ranks must call it."""
+    import torch.distributed as dist
+    d = replica_digest(flat)
+    both = torch.cat([d, ~d])
+    if dist.get_backend(process_group) != "nccl":
+        both = both.cpu()          # (a host backend would stage the 32 bytes itself)
+    dist.all_reduce(both, op=dist.ReduceOp.MAX, group=process_group)
+    both = both.cpu()
+    return bool(torch.equal(both[:2], ~both[2:]))
 
 
 class NativeComm:

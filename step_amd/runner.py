@@ -34,6 +34,11 @@ The pre-training stage (``step/TSFormer_*.py``) has the same slots: ``native_run
 ``CFG.DATASET_CLS = DevicePretrainingDataset`` (index-only ``(future_data, LongHistoryRef)`` batches, fused clip + Adam, loss + gradient +
 meters of an iteration from one ``TSFormer.pretrain_tail`` call).
 
+A launch on several GPUs (``CFG.GPU_NUM = 2``, the reference's default) hands the runner a ``DistributedDataParallel`` wrap, under which
+the reducer owns the gradients and all of the above but the loaders is off.  ``native_runner(..., native_data_parallel=True)`` takes the
+module out of the wrap in ``init_training`` and calls its ``enable_native_data_parallel()`` (the flat gradient buffer averaged inside
+backward), and checks once per epoch that the ranks' parameters are still the same bits (``step_amd.comm.replicas_identical``).
+
 Nothing here imports the reference or easytorch: the base class is handed in by the config file, which lives in the reference tree.
 """
 import math
@@ -278,7 +283,7 @@ class _Deferred:
 
 
 def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, encoder_workgroups=None, native_metrics=True,
-                  eval_cache_bytes=0, native_tail=False, native_pretrain=False):
+                  eval_cache_bytes=0, native_tail=False, native_pretrain=False, native_data_parallel=False, replica_check=True):
     """-> subclass of ``base`` (the reference's ``STEPRunner``, or any ``BaseTimeSeriesForecastingRunner``) for ``CFG.RUNNER``.
     ``encoder_workgroups``: compute units of the persistent encoder launch next to the step (None: 160 at 307 nodes / 336 tokens, the
     measured optimum of config C2; 0: one workgroup per sequence) -- only used while batches are prefetched.
@@ -296,7 +301,20 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
     the conditions of the STEP branch), and ``train_iters`` / ``val_iters`` take the loss, its gradient and the three meters from ONE
     ``TSFormer.pretrain_tail`` call (validation under ``no_grad``, nothing read back).  That needs the ``re_standard_transform`` scaler
     with scalar mean / std, ``masked_mae`` (basicts' or this package's) as the loss, only the three basicts metrics, a finite
-    ``null_val`` and no ``CFG.TRAIN.CL``; anything else takes the base class's path as with ``native_pretrain=False`` (the default)."""
+    ``null_val`` and no ``CFG.TRAIN.CL``; anything else takes the base class's path as with ``native_pretrain=False`` (the default).
+    ``native_data_parallel``: for a launch on several GPUs (``CFG.GPU_NUM = 2`` in fifteen of the reference's sixteen ``step/*.py``
+    configs), where easytorch wraps the model in ``DistributedDataParallel``.  ``init_training`` -- after easytorch has built Adam and
+    the scheduler and resumed a checkpoint -- takes the module out of the wrap and calls its ``enable_native_data_parallel()`` (rank 0's
+    resumed state is broadcast, the flat gradient buffer is averaged inside backward over RCCL's C API or ``torch.distributed``), so
+    that everything above acts as for one process: the fused optimizer, the native tail, ``native_pretrain``.  It acts only when
+    ``torch.distributed`` is initialised with more than one rank and EVERY rank holds a ``STEP``, or a ``TSFormer`` in pre-train mode,
+    on a GPU (one MIN all-reduce; otherwise nothing is unwrapped anywhere and rank 0 warns).  Checkpoints keep the reference's keys
+    either way.  The graph learner's time slices (``shard_graph_learner``) are not used under the runner.
+    ``replica_check``: with ``native_data_parallel`` acting, the first iteration of every epoch starts by comparing a 128-bit digest of
+    the ranks' flat parameter buffers (``step_amd.comm.replicas_identical``: one kernel, one 32-byte collective, one read-back); every
+    rank raises ``RuntimeError`` when they differ -- only rank 0 writes the checkpoint, and no wrapper guarantees identical replicas.
+    The buffer is the one the fused optimizer updates: where ``init_training`` keeps torch's optimizer there is none and nothing is
+    checked."""
 
     class NativeRunner(base):
         native_hooks = True
@@ -306,6 +324,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             self._deferring = False
             self._pending = {}          # meter name -> [(device value, n), ...] since the last flush
             self._metric_cache = None
+            self._dp_acting = False          # native_data_parallel took the module out of its DistributedDataParallel wrap
 
         # ---------------------------------------------------------------- loaders
         def _lookahead(self, loader, on):
@@ -379,8 +398,36 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             ok = (native_pretrain and isinstance(model, TSFormer) and model.mode == "pre-train" and next(model.parameters()).is_cuda)
             return model if ok else None
 
+        def _enable_data_parallel(self):
+            """native_data_parallel: the same decision on every rank, then unwrap and enable -> True when it acted"""
+            import torch.distributed as dist
+            if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+                return False
+            model = _unwrap(self.model)
+            able = ((isinstance(model, STEP) or (isinstance(model, TSFormer) and model.mode == "pre-train"))
+                    and next(model.parameters()).is_cuda)
+            # a mixed decision would deadlock the first collective: one MIN all-reduce before anyone acts
+            dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+            every = torch.tensor([1 if able else 0], dtype=torch.int32, device=dev)
+            dist.all_reduce(every, op=dist.ReduceOp.MIN)
+            if int(every.item()) == 0:
+                if dist.get_rank() == 0:
+                    import warnings
+                    warnings.warn("step_amd.runner: native_data_parallel needs a STEP, or a TSFormer in pre-train mode, on a GPU on every "
+                                  "rank; the model stays in its DistributedDataParallel wrap")
+                return False
+            if self.model is not model:
+                # no reference to the wrapper is kept: its reducer takes its autograd hooks with it.  The optimizer easytorch built holds
+                # the same Parameter objects, and save_model / load_model_resume branch on the wrap themselves
+                self.model = model
+                import gc
+                gc.collect()
+            model.enable_native_data_parallel(collectives="auto", sync_module_states=True)          # (after the resume: resumed weights are broadcast)
+            return True
+
         def init_training(self, cfg):
             super().init_training(cfg)
+            self._dp_acting = self._enable_data_parallel() if native_data_parallel else False
             model = _unwrap(self.model)
             opt = getattr(self, "optim", None)
             pretrain = self._pretrain_module() is not None
@@ -407,7 +454,21 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             del opt, g, sched          # the last references to the replaced Adam (its moments: two copies of the parameters)
 
         # ---------------------------------------------------------------- meters without a device synchronisation per iteration
+        def _check_replicas(self, epoch):
+            """every rank runs train_iters (validation and its hooks run on rank 0 only): all ranks see the same answer and raise together.
+            Without a flat parameter buffer (the fused optimizer was not swapped in: the same config decision on every rank) there is
+            nothing to digest and nothing is checked"""
+            import torch.distributed as dist
+            from .comm import replicas_identical
+            flat = _unwrap(self.model)._flat_param
+            if flat is not None and not replicas_identical(flat):
+                raise RuntimeError(f"step_amd.runner: the data-parallel replicas differ at the start of epoch {epoch} (rank "
+                                   f"{dist.get_rank()} of {dist.get_world_size()}): the ranks' flat parameter buffers do not hold the same "
+                                   "bits, so the checkpoint rank 0 writes is not what the other ranks trained")
+
         def train_iters(self, epoch, iter_index, data):
+            if self._dp_acting and replica_check and iter_index == 0:
+                self._check_replicas(epoch)
             self._deferring, self._metric_cache = defer_meters, None
             try:
                 scaler = self._tail_scaler() if native_tail else None

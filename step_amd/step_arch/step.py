@@ -911,58 +911,13 @@ class STEP(nn.Module):
         if self._comm is not None:
             self._comm.close()
             self._comm = None
-        on_gpu = self.backend.nodevec1.is_cuda
-        auto = collectives == "auto"
-        if auto:
-            collectives = "rccl" if (on_gpu and dist.get_backend(self._process_group) == "nccl") else "torch"
-        if collectives not in ("rccl", "torch"):
-            raise ValueError(f"collectives = {collectives!r}: expected 'auto', 'rccl' or 'torch'")
-        if collectives == "rccl" and dist.get_world_size(self._process_group) > self._min_world:
-            from .. import comm as _comm
-            if not on_gpu:
-                raise RuntimeError("collectives='rccl' needs the module on a GPU (move it first)")
-            if not _comm.available() and not auto:
-                raise RuntimeError("collectives='rccl': librccl could not be loaded into this process (STEP_RCCL_LIB names another copy)")
-            usable = _comm.available()
-            if auto and dist.get_world_size(self._process_group) > 1:
-                # agree BEFORE anyone enters ncclCommInitRank: a rank whose librccl did not load would otherwise go on to the all-reduce
-                # below while the others block in the communicator's rendezvous
-                have = torch.tensor([1 if usable else 0], device=self.backend.nodevec1.device, dtype=torch.int32)
-                dist.all_reduce(have, op=dist.ReduceOp.MIN, group=self._process_group)
-                usable = bool(int(have.item()))
-            try:
-                if not usable:
-                    raise RuntimeError("librccl could not be loaded on every rank")
-                self._comm = _comm.NativeComm(self._process_group)
-            except Exception as ex:          # noqa: BLE001
-                if not auto:
-                    raise
-                # "auto" promised a working data-parallel step, not a particular transport: say so and stay on torch.distributed
-                import warnings
-                warnings.warn(f"step_amd: RCCL C-API communicator could not be created ({ex}); the step's collectives stay on torch.distributed")
-                self._comm = None
-            if auto and dist.get_world_size(self._process_group) > 1:
-                # all ranks take the same transport: one rank without a communicator puts every rank on torch.distributed
-                ok = torch.tensor([1 if self._comm is not None else 0], device=self.backend.nodevec1.device, dtype=torch.int32)
-                dist.all_reduce(ok, op=dist.ReduceOp.MIN, group=self._process_group)
-                if int(ok.item()) == 0 and self._comm is not None:
-                    self._comm.close()
-                    self._comm = None
+        from .. import comm as _comm
+        self._comm = _comm.open_transport(self._process_group, collectives, self.backend.nodevec1.device, self._min_world)
         if self._comm is not None:
             # the all-reduce's stream: one that demonstrably overlaps with the compute stream (created AFTER RCCL's own streams exist)
             self._comm.use_side_stream(self._side_stream(self.backend.nodevec1.device, "comm"))
         if sync_module_states and dist.get_world_size(self._process_group) > self._min_world:
-            # what DistributedDataParallel does when it wraps a module: every rank starts from rank 0's parameters and buffers
-            src = dist.get_global_rank(self._process_group, 0)
-            with torch.no_grad():
-                for t in list(self.parameters()) + list(self.buffers()):
-                    d = t.detach()
-                    if d.is_contiguous():
-                        dist.broadcast(d, src, group=self._process_group)
-                    else:
-                        c = d.contiguous()
-                        dist.broadcast(c, src, group=self._process_group)
-                        d.copy_(c)
+            _comm.broadcast_module_states(self, self._process_group)
         if shard_graph_learner and dist.get_world_size(self._process_group) > self._min_world:
             # every rank keeps one time slice of the graph learner's global branch and of fc.weight
             if self.matmul_precision != "bf16":

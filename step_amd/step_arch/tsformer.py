@@ -440,6 +440,7 @@ class _PretrainFunction(torch.autograd.Function):
                    L.ptr(G["patch_embedding.input_embedding.bias"]), st)
             ctx.saved = None
             model._backward_count += 1
+            model._reduce_flat_grad(flat)          # data parallel: the views returned below then hold the group's mean
             return (None, None, None, None) + tuple(G[n] for n in model._pt_names)
         # scatter back to all token positions (zeros at masked ones), dropout, positional and patch embedding
         de = torch.zeros(S * P, 96, device=dev)
@@ -451,6 +452,7 @@ class _PretrainFunction(torch.autograd.Function):
         _linear_bwd(de, patches, None, G["patch_embedding.input_embedding.weight"].view(96, 12), G["patch_embedding.input_embedding.bias"])
         ctx.saved = None
         model._backward_count += 1
+        model._reduce_flat_grad(flat)
         return (None, None, None, None) + tuple(G[n] for n in model._pt_names)
 
 
@@ -543,6 +545,11 @@ class TSFormer(nn.Module):
         self._flat_param = None             # flatten_parameters(): all parameters as views into one buffer (FusedAdamClip)
         self._flat_grad = None
         self._backward_count = 0            # native backwards since zero_grad() (FusedAdamClip consumes exactly one)
+        # enable_native_data_parallel(): the group the pre-training backward averages its flat gradient over
+        self._process_group = None
+        self._min_world = 1
+        self._comm = None                   # step_amd.comm.NativeComm when the collectives are RCCL C-API calls
+        self._seed_rank = 0                 # this rank in the group: folded into the dropout seeds (_next_seed)
         self.fused_embed = os.environ.get("STEP_PT_FUSED_EMBED", "1") != "0"     # patch + positional embedding of the unmasked tokens only (both precisions)
         self.fused_proj = os.environ.get("STEP_PT_FUSED_PROJ", "1") != "0"       # qkv / out-projection and their data gradients as row kernels
         self.fused_ln = os.environ.get("STEP_PT_FUSED_LN", "1") != "0"           # residual add + dropout + LayerNorm as the output stage of the forward row kernels
@@ -852,8 +859,53 @@ class TSFormer(nn.Module):
         return self._pt_pool_buf, PT_POOL_WORDS
 
     def _next_seed(self):
+        # data parallel: one stream per rank (with one process-wide seed every rank would draw the same keep masks); rank 0's, and the
+        # stream of a module without a group, is the stream of a single process
         self._seed_ctr2 += 1
-        return (torch.initial_seed() * 6364136223846793005 + self._seed_ctr2 * 1442695040888963407) & ((1 << 63) - 1)
+        return (torch.initial_seed() * 6364136223846793005 + self._seed_ctr2 * 1442695040888963407
+                + self._seed_rank * 0x9E3779B97F4A7C15) & ((1 << 63) - 1)
+
+    # ------------------------------------------------------------------ data-parallel pre-training
+    def enable_native_data_parallel(self, process_group=None, sync_module_states=True, single_rank_collectives=False, collectives="auto"):
+        """Average the flat gradient buffer of the pre-training backward over the ranks of ``process_group`` (None: the default group)
+        before ``backward()`` returns: the ``.grad`` views autograd adopts and the buffer ``FusedAdamClip`` reads then hold the mean.
+        Replaces DistributedDataParallel's bucketed reducer (the reference: easytorch's wrap under ``CFG.GPU_NUM = 2``,
+        step/TSFormer_PEMS04.py) -- do not also wrap the module.  Same meaning as ``STEP.enable_native_data_parallel``:
+        ``sync_module_states`` broadcasts rank 0's parameters and buffers; ``collectives`` picks RCCL's C API ("rccl":
+        ``step_grad_allreduce_begin / _join`` on the whole buffer -- 2.67 MB at PEMS04, one chunk) or ``torch.distributed`` ("torch"),
+        "auto" by the group's backend with the all-rank agreement of ``step_amd.comm.open_transport``; a group of one rank issues nothing
+        unless ``single_rank_collectives`` is set.  The dropout seeds of the ranks differ from here on (rank 0's stay what they were);
+        the token masks come from Python's ``random`` per process, as in the reference.  A second call replaces the communicator."""
+        import torch.distributed as dist
+        from .. import comm as _comm
+        if self.mode != "pre-train":
+            raise ValueError("TSFormer.enable_native_data_parallel: the module is not in pre-train mode (in forecasting mode it is "
+                             "the frozen branch of STEP, which has its own enable_native_data_parallel)")
+        self._process_group = process_group if process_group is not None else dist.group.WORLD
+        self._min_world = 0 if single_rank_collectives else 1
+        if self._comm is not None:
+            self._comm.close()
+            self._comm = None
+        device = next(self.parameters()).device
+        self._comm = _comm.open_transport(self._process_group, collectives, device, self._min_world)
+        if sync_module_states and dist.get_world_size(self._process_group) > self._min_world:
+            _comm.broadcast_module_states(self, self._process_group)
+        self._seed_rank = dist.get_rank(self._process_group)
+
+    def _reduce_flat_grad(self, flat):
+        """the mean of the flat gradient buffer over the data-parallel group, in place, ordered on the current stream"""
+        if self._process_group is None:
+            return
+        import torch.distributed as dist
+        world = dist.get_world_size(self._process_group)
+        if world <= self._min_world:
+            return
+        if self._comm is not None:
+            self._comm.grad_allreduce_begin(flat)          # ncclAvg on the communicator's stream, behind the backward's kernels
+            self._comm.grad_allreduce_join()
+        else:
+            dist.all_reduce(flat, group=self._process_group)
+            flat.mul_(1.0 / world)
 
     def _pretrain_series(self, history_data):
         """history_data [B, L, N, C] (a device tensor or a ``LongHistoryRef``) -> (series [B*N, L] of the selected feature, B, N, L)"""

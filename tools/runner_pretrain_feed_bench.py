@@ -7,6 +7,8 @@ batch 16, bf16 mode, dropout on), timed.  One JSON line.  The pre-training sibli
 
 --runner native     CFG.RUNNER = step_amd.runner.native_runner(TSFormerRunner, native_pretrain=True)   (reference: TSFormerRunner as it is)
 --dataset device    CFG.DATASET_CLS = step_amd.runner.DevicePretrainingDataset                          (host: the reference's PretrainingDataset)
+--group-of-one      a process group of ONE rank (nccl = RCCL) and TSFormer.enable_native_data_parallel(single_rank_collectives=True): every
+                    collective of the data-parallel backward is issued (arithmetically a no-op) -- what the path costs on a one-GPU box
 """
 import argparse
 import importlib
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--iters", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--group-of-one", action="store_true")
     a = ap.parse_args()
     import torch
     from tests import dropin_common as DC
@@ -66,6 +69,14 @@ def main():
         torch.manual_seed(0)
         runner = cfg.RUNNER(cfg)
         runner.model.matmul_precision = "bf16"
+        transport = None
+        if a.group_of_one:
+            import torch.distributed as dist
+            os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+            os.environ.setdefault("MASTER_PORT", "29583")
+            dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", torch.cuda.current_device()))
+            runner.model.enable_native_data_parallel(single_rank_collectives=True)
+            transport = "rccl" if runner.model._comm is not None else "torch.distributed"
         t, calls, inner = {}, [0], runner.train_iters
 
         def train_iters(epoch, iter_index, data):          # (pretrain_tail does not go through the module's __call__: no forward hook)
@@ -80,7 +91,10 @@ def main():
         dt = time.perf_counter() - t["t0"]
         print(json.dumps({"runner": a.runner, "dataset": a.dataset, "ms_per_step": 1e3 * dt / a.iters, "windows_per_s": a.batch * a.iters / dt,
                           "iters": a.iters, "batch": a.batch, "final_loss": losses[-1],
-                          "optimizer": type(runner.optim).__name__, "dataset_cls": type(runner.train_data_loader.dataset).__name__}))
+                          "optimizer": type(runner.optim).__name__, "dataset_cls": type(runner.train_data_loader.dataset).__name__,
+                          "group_of_one": bool(a.group_of_one), "collectives": transport}))
+        if a.group_of_one:
+            dist.destroy_process_group()
 
 
 if __name__ == "__main__":
