@@ -16,6 +16,7 @@ the training configuration's: the host work of a forward is then shared by more 
 """
 import ctypes
 import math
+import numbers
 from dataclasses import dataclass
 
 import numpy as np
@@ -80,7 +81,15 @@ class EvalMetrics:
         self._acc.zero_()
         self.batches = 0
 
-    def update(self, pred, real):
+    def update(self, pred, real, group=None):
+        """one accumulate launch over the whole of ``pred`` / ``real``; with ``group = g`` one launch per ``g`` consecutive windows
+        (views of the two tensors, nothing is copied; the last group may be short), so that ``batches`` and ``batch_mean`` are what
+        separate updates of ``g`` windows each would have given: a loader that coalesces ``k`` batches of ``g`` windows into one
+        forward keeps the validation meters' per-loader-batch average"""
+        if group is not None:
+            if isinstance(group, bool) or not isinstance(group, numbers.Integral) or group < 1:
+                raise ValueError(f"EvalMetrics.update: group = {group!r} must be a positive integer (or None)")
+            group = int(group)
         p, r = _view3(pred, "pred"), _view3(real, "real")
         if p.shape != r.shape or p.shape[1] != self.horizons or 0 in p.shape:
             raise ValueError(f"EvalMetrics.update: pred {tuple(pred.shape)} and real {tuple(real.shape)} must be one non-empty "
@@ -88,9 +97,14 @@ class EvalMetrics:
         if p.device != self._acc.device or r.device != self._acc.device:
             raise ValueError(f"EvalMetrics.update: tensors on {p.device} / {r.device}, accumulator on {self._acc.device}")
         B, H, N = p.shape
-        _lib.call("step_eval_metrics_accumulate", ctypes.c_void_p(p.data_ptr()), *_strides(p, "pred"), ctypes.c_void_p(r.data_ptr()),
-                  *_strides(r, "real"), B, H, N, self.scale, self.shift, self.null_val, _lib.ptr(self._acc), _lib.stream())
-        self.batches += 1
+        ps, rs = _strides(p, "pred"), _strides(r, "real")          # (checked on the whole tensors: refused before anything is launched)
+        g = B if group is None else min(group, B)
+        for at in range(0, B, g):
+            n = min(g, B - at)
+            _lib.call("step_eval_metrics_accumulate", ctypes.c_void_p(p.data_ptr() + 4 * at * ps[0]), *ps,
+                      ctypes.c_void_p(r.data_ptr() + 4 * at * rs[0]), *rs, n, H, N, self.scale, self.shift, self.null_val,
+                      _lib.ptr(self._acc), _lib.stream())
+            self.batches += 1
 
     def result(self, horizons=None):
         """the single device-to-host copy of the pass; the accumulator stays as it is (more updates may follow)"""

@@ -34,6 +34,11 @@ The pre-training stage (``step/TSFormer_*.py``) has the same slots: ``native_run
 ``CFG.DATASET_CLS = DevicePretrainingDataset`` (index-only ``(future_data, LongHistoryRef)`` batches, fused clip + Adam, loss + gradient +
 meters of an iteration from one ``TSFormer.pretrain_tail`` call).
 
+The validation pass of the forecasting stage (``base_tsf_runner.py:257-273``: three metric functions and three ``.item()`` per batch of 8
+windows) has two switches of its own, both off by default: ``native_eval=True`` takes the ``val_`` meters from one
+``step_amd.EvalMetrics`` per pass (one launch per batch, one read-back per pass), ``eval_batch_size=E`` lets the look-ahead loader
+concatenate batches of origins so that a validation / test forward carries ``E`` windows.
+
 A launch on several GPUs (``CFG.GPU_NUM = 2``, the reference's default) hands the runner a ``DistributedDataParallel`` wrap, under which
 the reducer owns the gradients and all of the above but the loaders is off.  ``native_runner(..., native_data_parallel=True)`` takes the
 module out of the wrap in ``init_training`` and calls its ``enable_native_data_parallel()`` (the flat gradient buffer averaged inside
@@ -174,19 +179,62 @@ class DevicePretrainingDataset(Dataset):
         return self._loaders[key]
 
 
+def coalesce_origin_batches(iterable, k):
+    """Yields the batches of ``iterable`` -- 1-D int64 tensors of forecast origins -- ``k`` at a time, concatenated in order on the
+    host; the last yield holds what is left (fewer batches, and the loader's last batch may itself be short).  ``k = 1`` hands every
+    batch through as the object it is."""
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"coalesce_origin_batches: k = {k} must be at least 1")
+    if k == 1:
+        yield from iterable
+        return
+    held = []
+    for batch in iterable:
+        held.append(batch)
+        if len(held) == k:
+            yield torch.cat(held)
+            held = []
+    if held:
+        yield held[0] if len(held) == 1 else torch.cat(held)
+
+
+def coalesce_factor(eval_batch_size, loader):
+    """how many consecutive batches of ``loader`` make one forward of about ``eval_batch_size`` windows: ``max(1, E // batch_size)``
+    where the loader's dataset is index-only (its batches are origins, cheap to concatenate before they are staged) and the loader has
+    an integer ``batch_size``; 1 (``eval_batch_size`` is ignored) for anything else"""
+    if eval_batch_size is None or loader is None or not getattr(getattr(loader, "dataset", None), "index_only", False):
+        return 1
+    b = getattr(loader, "batch_size", None)
+    if isinstance(b, bool) or not isinstance(b, numbers.Integral) or b < 1:
+        return 1
+    return max(1, int(eval_batch_size) // int(b))
+
+
 class LookaheadLoader:
     """Iterates ``loader`` one batch ahead of its consumer (see the module docstring).  ``runner`` supplies the device
-    (``to_running_device``) and the model; ``prefetch=False`` only stages the batches on the device."""
+    (``to_running_device``) and the model; ``prefetch=False`` only stages the batches on the device.  ``coalesce = k > 1``: ``k``
+    consecutive batches of origins of an index-only dataset are concatenated on the host and staged as ONE batch (their host origins
+    travel with it as before); ``group_size`` is the wrapped loader's own batch size."""
 
-    def __init__(self, loader, runner, prefetch=True):
+    def __init__(self, loader, runner, prefetch=True, coalesce=1):
         self.loader, self.runner, self.prefetch = loader, runner, prefetch
         self.dataset = getattr(loader, "dataset", None)
+        self.coalesce = int(coalesce)
+        if self.coalesce < 1:
+            raise ValueError(f"LookaheadLoader: coalesce = {coalesce} must be at least 1")
+        if self.coalesce > 1 and not getattr(self.dataset, "index_only", False):
+            raise ValueError("LookaheadLoader: only batches of origins (an index-only dataset) can be coalesced")
         self._copy_stream = None
         self.staged_batches = 0
         self.prefetched_batches = 0
 
     def __len__(self):
-        return len(self.loader)
+        return -(-len(self.loader) // self.coalesce)
+
+    @property
+    def group_size(self):
+        return getattr(self.loader, "batch_size", None)
 
     def __getattr__(self, name):          # batch_size, sampler, ... of the wrapped loader (easytorch reads a few)
         return getattr(self.__dict__["loader"], name)
@@ -236,7 +284,7 @@ class LookaheadLoader:
         self.prefetched_batches += 1
 
     def __iter__(self):
-        it = iter(self.loader)
+        it = iter(self.loader) if self.coalesce == 1 else coalesce_origin_batches(self.loader, self.coalesce)
         try:
             nxt = self._stage(next(it))
         except StopIteration:
@@ -283,7 +331,8 @@ class _Deferred:
 
 
 def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, encoder_workgroups=None, native_metrics=True,
-                  eval_cache_bytes=0, native_tail=False, native_pretrain=False, native_data_parallel=False, replica_check=True):
+                  eval_cache_bytes=0, native_tail=False, native_pretrain=False, native_data_parallel=False, replica_check=True,
+                  native_eval=False, eval_batch_size=None):
     """-> subclass of ``base`` (the reference's ``STEPRunner``, or any ``BaseTimeSeriesForecastingRunner``) for ``CFG.RUNNER``.
     ``encoder_workgroups``: compute units of the persistent encoder launch next to the step (None: 160 at 307 nodes / 336 tokens, the
     measured optimum of config C2; 0: one workgroup per sequence) -- only used while batches are prefetched.
@@ -314,7 +363,22 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
     the ranks' flat parameter buffers (``step_amd.comm.replicas_identical``: one kernel, one 32-byte collective, one read-back); every
     rank raises ``RuntimeError`` when they differ -- only rank 0 writes the checkpoint, and no wrapper guarantees identical replicas.
     The buffer is the one the fused optimizer updates: where ``init_training`` keeps torch's optimizer there is none and nothing is
-    checked."""
+    checked.
+    ``native_eval``: the validation meters of the forecasting stage come from one ``step_amd.EvalMetrics`` per pass -- ``val_iters``
+    queues ONE accumulate launch on the model's normalised prediction and the batch's target view (no rescale, no metric functions, no
+    ``.item()``), and ``flush_meters`` reads the mean of the per-batch values back once per pass, before ``save_best_model`` looks at
+    ``val_MAE``.  Needs a ``STEP`` module on a GPU, the ``re_standard_transform`` scaler with scalar mean / std, only the three basicts
+    metrics and a real ``null_val`` (NaN included); anything else takes the base class's ``val_iters`` as with ``native_eval=False``
+    (the default).  Under ``native_pretrain`` the runner's ``test()`` (``TSFormerRunner.test``) likewise takes the three ``test_``
+    meters of a batch from one ``pretrain_tail`` call and reads nothing back before the meters are printed.
+    ``eval_batch_size``: ``E`` windows per validation / test forward instead of the config's ``VAL/TEST.DATA.BATCH_SIZE``: the look-ahead
+    loader concatenates ``max(1, E // batch_size)`` consecutive batches of origins before it stages them, ``native_eval`` still
+    accumulates per loader batch (the ``val_`` meters stay the mean over the config's batches, ``n`` their count), and the reference's
+    ``test()`` evaluates the concatenation of whatever arrives.  Only for index-only datasets (``DeviceForecastingDataset``) behind a
+    loader with an integer ``batch_size`` -- ignored otherwise, and never applied to a ``TSFormer``'s loaders (a pre-training forward
+    draws one mask).  Off by default (None) because it is not the same pass: the graph learner samples in eval mode too, its Gumbel
+    noise is a function of the forward count and the position in the batch, so a coalesced pass draws other noise than the uncoalesced
+    one -- as another seed would."""
 
     class NativeRunner(base):
         native_hooks = True
@@ -325,6 +389,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             self._pending = {}          # meter name -> [(device value, n), ...] since the last flush
             self._metric_cache = None
             self._dp_acting = False          # native_data_parallel took the module out of its DistributedDataParallel wrap
+            self._val_metrics = None          # native_eval: (what it was built for, the validation pass's EvalMetrics)
 
         # ---------------------------------------------------------------- loaders
         def _lookahead(self, loader, on):
@@ -346,13 +411,21 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             if eval_cache_bytes > 0 and isinstance(model, STEP):
                 model.eval_cache_bytes = int(eval_cache_bytes)
 
+        def _eval_lookahead(self, loader):
+            """the validation / test loader: staged, not announced; ``eval_batch_size`` coalesces origin batches -- never a
+            pre-training loader's (one forward of a TSFormer in pre-train mode draws ONE mask for all its windows)"""
+            if loader is None:
+                return None
+            k = 1 if isinstance(_unwrap(self.model), TSFormer) else coalesce_factor(eval_batch_size, loader)
+            return LookaheadLoader(loader, self, prefetch=False, coalesce=k)
+
         def build_val_data_loader(self, cfg):
             self._enable_eval_cache()
-            return self._lookahead(super().build_val_data_loader(cfg), False)
+            return self._eval_lookahead(super().build_val_data_loader(cfg))
 
         def build_test_data_loader(self, cfg):
             self._enable_eval_cache()
-            return self._lookahead(super().build_test_data_loader(cfg), False)
+            return self._eval_lookahead(super().build_test_data_loader(cfg))
 
         # ---------------------------------------------------------------- feature selection without a host-device synchronisation
         # ``data[:, :, :, [0, 1, 2]]`` (step_runner.py:25-26,39-40) builds an index tensor on the host and copies it to the device: a blocking
@@ -498,9 +571,8 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                 return None
             return self._scalar_rescale(("step_loss", "step_loss_native"))
 
-        def _scalar_rescale(self, loss_names):
-            """(mean, std) of a ``re_standard_transform`` scaler with scalar arguments when the loss is one of ``loss_names``, the metrics
-            are the three of basicts and ``null_val`` is finite, else None"""
+        def _scaler_mean_std(self):
+            """(mean, std) of a ``re_standard_transform`` scaler with scalar real arguments, else None"""
             scaler = getattr(self, "scaler", None)
             if not isinstance(scaler, dict):
                 return None
@@ -510,15 +582,78 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             mean, std = args.get("mean"), args.get("std")
             if isinstance(mean, bool) or isinstance(std, bool) or not (isinstance(mean, numbers.Real) and isinstance(std, numbers.Real)):
                 return None
-            if getattr(self.loss, "__name__", None) not in loss_names:
-                return None
+            return float(mean), float(std)
+
+        def _only_basicts_metrics(self):
             metrics = getattr(self, "metrics", None)
-            if not isinstance(metrics, dict) or not all(self._is_basicts_metric(f) for f in metrics.values()):
+            return isinstance(metrics, dict) and all(self._is_basicts_metric(f) for f in metrics.values())
+
+        def _scalar_rescale(self, loss_names):
+            """(mean, std) of a ``re_standard_transform`` scaler with scalar arguments when the loss is one of ``loss_names``, the metrics
+            are the three of basicts and ``null_val`` is finite, else None"""
+            scaler = self._scaler_mean_std()
+            if scaler is None or getattr(self.loss, "__name__", None) not in loss_names or not self._only_basicts_metrics():
                 return None
             nv = getattr(self, "null_val", 0.0)
             if not (isinstance(nv, numbers.Real) and math.isfinite(nv)):
                 return None
-            return float(mean), float(std)
+            return scaler
+
+        # ---------------------------------------------------------------- validation meters on the device (native_eval=True)
+        def _eval_scaler(self):
+            """(mean, std) when everything known BEFORE the forward pass allows the validation meters to come from ``EvalMetrics``,
+            else None.  The loss plays no part in a validation pass, and ``null_val`` may be NaN (the reference's default)"""
+            if not native_eval:
+                return None
+            model = _unwrap(self.model)
+            if not (isinstance(model, STEP) and next(model.parameters()).is_cuda):
+                return None
+            scaler = self._scaler_mean_std()
+            nv = getattr(self, "null_val", 0.0)
+            if scaler is None or not self._only_basicts_metrics() or isinstance(nv, bool) or not isinstance(nv, numbers.Real):
+                return None
+            return scaler
+
+        def _val_accumulator(self, horizons, mean, std, device):
+            """the pass's ``EvalMetrics``: made on first use, kept over the epochs, made anew when what it was built for changes"""
+            key = (int(horizons), repr(float(self.null_val)), std, mean, device)
+            if self._val_metrics is None or self._val_metrics[0] != key:
+                self._drain_val_metrics()          # (nothing to drain unless the key changed in the middle of a pass)
+                from .evaluate import EvalMetrics
+                self._val_metrics = (key, EvalMetrics(horizons, float(self.null_val), rescale=(std, mean), device=device))
+            return self._val_metrics[1]
+
+        def _drain_val_metrics(self):
+            """the pass's single device-to-host copy: the mean of the per-batch values goes to the ``val_`` meters"""
+            m = self._val_metrics[1] if self._val_metrics is not None else None
+            if m is None or m.batches == 0:
+                return
+            res = m.result()
+            for metric_name, metric_func in self.metrics.items():
+                super().update_epoch_meter("val_" + metric_name, float(res.batch_mean[self._NATIVE_METRICS[metric_func.__name__]]), n=res.batches)
+            m.reset()
+
+        def _native_eval_iters(self, data, scaler):
+            """base_tsf_runner.py:257-273 with the rescaling and the three metrics in one ``EvalMetrics.update``, nothing read back"""
+            from .evaluate import MAX_HORIZONS
+            mean, std = scaler
+            forward_return = self.forward(data=data, epoch=None, iter_num=None, train=False)
+            pred, real = forward_return[0], forward_return[1]
+            ok = (torch.is_tensor(pred) and torch.is_tensor(real) and pred.is_cuda and real.is_cuda and pred.device == real.device
+                  and pred.dtype == torch.float32 and real.dtype == torch.float32 and pred.dim() == 4 and pred.shape[3] == 1
+                  and pred.shape == real.shape and 0 not in pred.shape and pred.shape[1] <= MAX_HORIZONS
+                  and all(st > 0 for t in (pred, real) for size, st in zip(t.shape, t.stride()) if size > 1))
+            if not ok:
+                # the forward pass is done and cannot be repeated: the base class's tail (:267-273) on torch ops, the scaler being
+                # re_standard_transform with scalar mean / std (basicts/data/transform.py:59-65)
+                prediction_rescaled, real_value_rescaled = pred * std + mean, real * std + mean
+                for metric_name, metric_func in self.metrics.items():
+                    metric_item = self.metric_forward(metric_func, [prediction_rescaled, real_value_rescaled])
+                    self.update_epoch_meter("val_" + metric_name, metric_item.item())
+                return
+            loader = getattr(self, "val_data_loader", None)
+            group = loader.group_size if isinstance(loader, LookaheadLoader) and loader.coalesce > 1 else None
+            self._val_accumulator(pred.shape[1], mean, std, pred.device).update(pred, real, group=group)
 
         # ---------------------------------------------------------------- TSFormer pre-training (native_pretrain=True)
         def _pretrain_scaler(self, data):
@@ -539,11 +674,36 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
         def val_iters(self, iter_index, data):
             scaler = self._pretrain_scaler(data) if native_pretrain else None
             if scaler is None:
+                scaler = self._eval_scaler()
+                if scaler is not None:
+                    return self._native_eval_iters(data, scaler)
                 return super().val_iters(iter_index, data)
             with torch.no_grad():
                 _, three = self._pretrain_tail(data, scaler)
             for metric_name, metric_func in self.metrics.items():          # fed with the other deferred values when the epoch's meters are printed
                 self.update_epoch_meter("val_" + metric_name, _Deferred(three[self._NATIVE_METRICS[metric_func.__name__]]))
+
+        def test(self, *args, **kwargs):
+            """``TSFormerRunner.test`` (step/step_runner/tsformer_runner.py:73-90) under ``native_pretrain``: one ``pretrain_tail`` call per
+            batch, the three ``test_`` meters queued on the device like the validation ones.  Every other runner's ``test()`` is its own"""
+            if self._pretrain_module() is None:
+                return super().test(*args, **kwargs)
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+                return None          # (the reference's test() is master_only)
+            batches = iter(self.test_data_loader)
+            data = next(batches, None)
+            scaler = None if data is None else self._pretrain_scaler(data)          # (the batch form: a loader's batches all have one)
+            if scaler is None:
+                del batches
+                return super().test(*args, **kwargs)
+            with torch.no_grad():
+                while data is not None:
+                    _, three = self._pretrain_tail(data, scaler)
+                    for metric_name, metric_func in self.metrics.items():
+                        self.update_epoch_meter("test_" + metric_name, _Deferred(three[self._NATIVE_METRICS[metric_func.__name__]]))
+                    data = next(batches, None)
+            return None
 
         def _native_tail_iters(self, epoch, iter_index, data, scaler):
             """base_tsf_runner.py:237-255 with the rescaling, the curriculum slice, the loss and the three metrics in one train_tail call"""
@@ -602,7 +762,8 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             super().update_epoch_meter(name, value, n)
 
         def flush_meters(self):
-            """feed the deferred values to the epoch meters (one device synchronisation for all of them)"""
+            """feed the deferred values to the epoch meters (one device synchronisation for all of them), then what a ``native_eval``
+            validation pass accumulated (its one read-back)"""
             pending, self._pending = self._pending, {}
             if pending:
                 means, counts = [], []
@@ -613,6 +774,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                     counts.append(sum(n for _, n in items))
                 for name, m, c in zip(pending, torch.stack(means).cpu().tolist(), counts):
                     super().update_epoch_meter(name, m, c)
+            self._drain_val_metrics()
 
         def print_epoch_meters(self, meter_type):
             self.flush_meters()
