@@ -7,6 +7,7 @@
 // parameters / moments / gradients (16 B read + 12 B written per element: HBM-bound).
 #include "common.h"
 #include "step_internal.h"
+#include "tail_device.h"
 
 namespace {
 
@@ -136,7 +137,9 @@ static int adam_clip_launch(float* params, const float* grads, float* exp_avg, f
 
 // ---------------------------------------------------------------------------------------------------------
 // step_loss (reference step/step_loss/step_loss.py:5-16 + basicts/metrics/mae.py:5-28), forward value and both
-// gradients in two launches:  loss = sum(|p - y| m) / sum(m) + coef * mean(BCE(theta, prior)),  m = |y - null| > 5e-5.
+// gradients in two launches:  loss = sum(|p - y| m) / sum(m) + coef * mean(BCE(theta, prior)),  m = !(|y - null| <= 5e-5).
+// Rescaled element, mask and NaN conventions are those of csrc/tail_device.h (two roundings in x * scale + shift; a NaN label counts, a NaN
+// term adds 0 and has gradient 0).
 namespace {
 __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restrict__ pred, const float* __restrict__ real, long n1, long rs,
                                                           float scale, float shift,
@@ -146,8 +149,12 @@ __global__ __launch_bounds__(256) void loss_reduce_kernel(const float* __restric
     double s_abs = 0.0, s_cnt = 0.0, s_bce = 0.0;
     const long stride = (long)gridDim.x * 256;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n1; i += stride) {
-        const float y = real[i * rs] * scale + shift;
-        if (fabsf(y - null_val) > 5e-5f) { s_abs += fabsf((pred[i] * scale + shift) - y); s_cnt += 1.0; }
+        const TailElem e = tail_rescale(pred[i], real[i * rs], scale, shift, null_val);
+        if (e.m) {
+            const float ad = fabsf(e.p - e.y);
+            if (!isnan(ad)) s_abs += ad;          // where(isnan(loss), 0, loss), mae.py:27: the element still counts
+            s_cnt += 1.0;
+        }
     }
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n2; i += stride) {
         const float t = theta[i], y = prior[i];
@@ -169,14 +176,12 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(const float* __restric
                                                           const StepDynState* __restrict__ dyn) {
     if (dyn) coef = dyn->gsl_coef;      // replayed steps (step_hip.h)
     const double cnt = acc[1];
-    const float inv_cnt = cnt > 0.0 ? (float)(1.0 / cnt) : 0.f;
+    const float g = cnt > 0.0 ? (float)(1.0 / cnt) * scale : 0.f;      // d/d pred of the loss on pred * scale + shift
     if (blockIdx.x == 0 && threadIdx.x == 0)
         *loss = (cnt > 0.0 ? (float)(acc[0] / cnt) : 0.f) + coef * (float)(acc[2] / (double)n2);
     const long stride = (long)gridDim.x * 256;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n1; i += stride) {
-        const float y = real[i * rs] * scale + shift, d = (pred[i] * scale + shift) - y;
-        const float m = fabsf(y - null_val) > 5e-5f ? inv_cnt * scale : 0.f;      // d/d pred of the loss on pred * scale + shift
-        dpred[i] = d > 0.f ? m : (d < 0.f ? -m : 0.f);
+        dpred[i] = tail_sign_grad(tail_rescale(pred[i], real[i * rs], scale, shift, null_val), g);
     }
     const float sc = coef / (float)n2;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n2; i += stride) {
@@ -235,10 +240,10 @@ extern "C" int step_loss_fwd_bwd(const float* pred, const float* real, long n_pr
 }
 // The three training metrics the reference's runner evaluates every iteration (base_tsf_runner.py:252-254: masked_mae, masked_rmse,
 // masked_mape of basicts/metrics -- ~30 element-wise torch launches) in ONE launch:
-//   m  = |y - null| > 5e-5                       (mae.py:18-21, rmse.py:17-20: ~isclose(y, null, atol 5e-5, rtol 0))
+//   m  = !(|y - null| <= 5e-5)                   (mae.py:18-21, rmse.py:17-20: ~isclose(y, null, atol 5e-5, rtol 0); a NaN label counts)
 //   MAE = sum |p - y| m / sum m,  RMSE = sqrt(sum (p - y)^2 m / sum m)
-//   y0 = |y| < 1e-4 ? 0 : y,  m0 = |y0| > 5e-5,  MAPE = sum |(|p - y0|) / y0| m0 / sum m0          (mape.py:21-35, null value fixed at 0)
-// (an all-masked batch gives 0, like the reference's nan -> 0 replacement).  work: 6 doubles, ZERO before the first call; the last block to
+//   y0 = |y| < 1e-4 ? 0 : y,  m0 = !(|y0| <= 5e-5),  MAPE = sum |(|p - y0|) / y0| m0 / sum m0     (mape.py:21-35, null value fixed at 0)
+// (an all-masked batch gives 0, and a NaN term adds 0, like the reference's nan -> 0 replacement: tail_accumulate of csrc/tail_device.h).  work: 6 doubles, ZERO before the first call; the last block to
 // finish turns the sums into out[0..2] and clears them again, so no memset is queued per call.
 namespace {
 __global__ __launch_bounds__(256) void masked_metrics_kernel(const float* __restrict__ pred, long ps, const float* __restrict__ real, long rs, long n,
@@ -248,10 +253,11 @@ __global__ __launch_bounds__(256) void masked_metrics_kernel(const float* __rest
     double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     const long stride = (long)gridDim.x * 256;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        const float p = pred[i * ps], y = real[i * rs];
-        if (fabsf(y - null_val) > 5e-5f) { const float d = p - y; a[0] += fabsf(d); a[1] += (double)d * d; a[2] += 1.0; }
-        const float y0 = fabsf(y) < 1e-4f ? 0.f : y;
-        if (fabsf(y0) > 5e-5f) { a[3] += fabsf(fabsf(p - y0) / y0); a[4] += 1.0; }
+        TailElem e;          // the caller has rescaled both already
+        e.p = pred[i * ps];
+        e.y = real[i * rs];
+        e.m = !(fabsf(e.y - null_val) <= 5e-5f);
+        tail_accumulate(e, a);
     }
 #pragma unroll
     for (int k = 0; k < 5; ++k)

@@ -14,7 +14,7 @@ def masked_mae(preds, labels, null_val=np.nan):
     if np.isnan(null_val):
         mask = ~torch.isnan(labels)
     else:
-        mask = (labels - null_val).abs() > 5e-5          # ~isclose(labels, null_val, atol=5e-5, rtol=0)
+        mask = ~((labels - null_val).abs() <= 5e-5)          # ~isclose(labels, null_val, atol=5e-5, rtol=0): a NaN label counts
     mask = mask.float()
     mask = mask / torch.mean(mask)
     mask = torch.nan_to_num(mask, nan=0.0)
@@ -86,6 +86,7 @@ def step_loss_native(prediction, real_value, theta, priori_adj, gsl_coefficient,
     the runner's inverse scaling (base_tsf_runner.py:240-250, step_runner.py:86-92) done inside the loss kernels instead of four
     element-wise launches before them and their autograd nodes after; ``real_value`` may be one feature of the batch tensor
     (``future[..., :1]``), it is read in place.
+    NaNs follow the reference: a NaN label is not close to ``null_val``, so it counts in the denominator; a NaN ``|p - y|`` adds 0 and has gradient 0.
     ``horizons=k``: the loss of ``train_tail`` on the first ``k`` horizon steps of the FULL tensors (curriculum learning)."""
     if horizons is not None:
         return train_tail(prediction, real_value, theta, priori_adj, gsl_coefficient, null_val=null_val, rescale=rescale, horizons=horizons)[0]

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import direct_ref as D
+from tests import optim_ref as R
 from tests.helpers import load_golden, rel_l2
 from tests.test_gpu_step import build_native, inputs_of
 
@@ -31,6 +33,31 @@ def _setup(mode, dropout):
     return g, m, opt
 
 
+def _adam_state(model, opt):
+    return tuple(t.detach().cpu().clone() for t in (model._flat_param, opt.exp_avg, opt.exp_avg_sq))
+
+
+def _check_replayed_adam(cmp, tag, before, model, opt, step):
+    """The graph-captured clip + Adam (step_adam_clip_dyn behind step_dyn_advance) against tests/optim_ref.py: the replay's OWN flat
+    gradient, the device's step count and the optimizer's hyperparameters go into adam_clip_ref in float64 and float32, and the replay's
+    parameter update and moments are held to the rule of tests/test_gpu_optim_direct.py -- no second, independently rounded gradient
+    is involved.  A replay that is off by one in the step count, ignores the clip or reads a stale learning rate fails here."""
+    pg = opt.param_groups[0]
+    kw = dict(lr=R.abi_float(pg["lr"]), betas=R.abi_float(pg["betas"]), eps=R.abi_float(pg["eps"]), wd=R.abi_float(pg["weight_decay"]),
+              step=step.state()["adam_step"], max_norm=R.abi_float(opt.max_norm))
+    g = model._flat_grad.detach().cpu()
+    after = _adam_state(model, opt)
+    r64, r32 = (R.adam_clip_ref(dt, before[0], g, before[1], before[2], **kw) for dt in (torch.float64, torch.float32))
+    p64 = before[0].double()
+    cmp.add(f"{tag} update", after[0].double() - p64, r64[0] - p64, r32[0].double() - p64)
+    cmp.add(f"{tag} m", after[1], r64[1], r32[1])
+    cmp.add(f"{tag} v", after[2], r64[2], r32[2])
+    norm = float(opt.grad_norm.cpu())
+    print(f"RATIO {tag}: adam_step {kw['step']} lr {kw['lr']} gradient norm {norm:.6g} (float64 {float(r64[3]):.6g}), clip active: {norm > opt.max_norm}")
+    assert norm == pytest.approx(float(r64[3]), rel=1e-5)
+    return norm > opt.max_norm
+
+
 @pytest.mark.parametrize("mode", ["f32", "bf16"])
 def test_replay_matches_eager_step(mode):
     from step_amd import GraphedTrainStep
@@ -42,6 +69,7 @@ def test_replay_matches_eager_step(mode):
     step = GraphedTrainStep(model, opt, (hist, long_hist, fut), scaler=(mean, std), epoch=1, warmup=2)
     assert step.state()["adam_step"] == 2
     rng = np.random.default_rng(0)
+    cmp = D.Compare(f"replayed adam [{mode}]", R.ADAM_M, R.ADAM_FLOOR, 0.0)
     for k in range(3):
         # a different batch every time: the static input buffers are refilled, not re-captured
         hk = hist + torch.from_numpy(rng.normal(size=tuple(hist.shape)).astype(np.float32)).cuda() * 0.05
@@ -49,8 +77,11 @@ def test_replay_matches_eager_step(mode):
         lk[..., 0] += torch.from_numpy(rng.normal(size=tuple(long_hist.shape[:-1])).astype(np.float32)).cuda() * 0.05
         with torch.no_grad():
             twin._flat_param.copy_(model._flat_param)                       # the parameters this replay starts from
+        before = _adam_state(model, opt)
         loss = step(hk, lk, fut)
         g_graph = model._flat_grad.clone()
+        _check_replayed_adam(cmp, f"replay {k}", before, model, opt, step)
+        assert step.state()["adam_step"] == 3 + k
         topt.zero_grad(set_to_none=True)
         pred, theta, knn, coef = twin(history_data=hk, long_history_data=lk, future_data=None, batch_seen=k, epoch=1)
         l2 = step_loss_native(pred[..., :1], fut[..., :1], theta, knn, coef, null_val=0.0, rescale=(mean, std))
@@ -69,8 +100,11 @@ def test_replay_matches_eager_step(mode):
     d_full = float((model._flat_param - before).norm())
     step.set_lr(2e-5)
     before = model._flat_param.clone()
+    state = _adam_state(model, opt)
     step(hist, long_hist, fut)
     d_small = float((model._flat_param - before).norm())
+    _check_replayed_adam(cmp, "replay at lr 2e-5", state, model, opt, step)
+    cmp.finish()
     print(f"[{mode}] |delta params| at lr 2e-3: {d_full:.4e}, at lr 2e-5: {d_small:.4e}")
     assert 30.0 < d_full / d_small < 300.0
     l_e1 = float(step(hist, long_hist, fut))

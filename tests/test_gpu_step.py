@@ -408,23 +408,10 @@ def test_wavenet_phase_5_plus_6_is_phase_1(mode):
 
 
 def test_native_masked_metrics_match_the_reference_definitions():
-    """step_masked_metrics: MAE / RMSE / MAPE of basicts/metrics/{mae,rmse,mape}.py (restated below line by line) from one launch,
-    including null values, labels below 1e-4 (MAPE zeroes and masks them), a strided label view and an all-masked batch."""
+    """step_masked_metrics: MAE / RMSE / MAPE of basicts/metrics/{mae,rmse,mape}.py (restated line by line in tests/optim_ref.py) from
+    one launch, including null values, labels below 1e-4 (MAPE zeroes and masks them), a strided label view and an all-masked batch."""
     from step_amd.step_loss import masked_metrics_native
-
-    def ref(p, y, null):
-        def mask_of(lab, nv):
-            m = (~torch.isclose(lab, torch.tensor(nv).expand_as(lab), atol=5e-5, rtol=0.)).float()
-            m = m / m.mean()
-            return torch.where(torch.isnan(m), torch.zeros_like(m), m)
-        m = mask_of(y, null)
-        mae = torch.nan_to_num(torch.abs(p - y) * m, nan=0.0).mean()
-        mse = torch.nan_to_num((p - y) ** 2 * m, nan=0.0).mean()
-        y0 = torch.where(torch.abs(y) < 1e-4, torch.zeros_like(y), y)
-        m0 = mask_of(y0, 0.0)
-        ape = torch.abs(torch.abs(p - y0) / y0) * m0
-        mape = torch.where(torch.isnan(ape), torch.zeros_like(ape), ape).mean()
-        return torch.stack([mae, torch.sqrt(mse), mape])
+    from tests.optim_ref import masked_metrics_ref as ref
     gen = torch.Generator().manual_seed(3)
     for shape, null in (((8, 12, 307, 1), 0.0), ((3, 12, 37, 1), 0.0), ((2, 12, 20, 1), -1.0)):
         y3 = torch.randn(*shape[:3], 3, generator=gen) * 50 + 100

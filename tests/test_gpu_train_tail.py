@@ -137,7 +137,7 @@ def test_work_buffer_is_left_clean_and_is_per_stream():
         assert torch.equal(x, y)
 
 
-@pytest.mark.parametrize("c", ("a", "b", "c"))
+@pytest.mark.parametrize("c", CASES)
 def test_all_horizons_agree_with_the_existing_native_path(c):
     from step_amd.step_loss import masked_metrics_native, step_loss_native
     z, d = fixture(), device_case(c)
@@ -149,8 +149,9 @@ def test_all_horizons_agree_with_the_existing_native_path(c):
     odp, odt = torch.autograd.grad(old, [pred, theta])
     om = masked_metrics_native(pred.detach() * std + mean, real * std + mean, 0.0)
     loss, metrics, dp, dt = result(c, 12)
-    assert float(loss) == pytest.approx(float(old.detach()), rel=1e-5)
+    assert float(loss) == pytest.approx(float(old.detach()), rel=1e-5)          # (finite for d, e0 and e11 as well: nan never equals nan)
     assert rel_l2(dp, odp[..., 0]) < 1e-5 and rel_l2(dt, odt) < 1e-5
+    assert torch.equal(dp != 0, odp[..., 0] != 0)                          # the same labels masked, the same NaN terms without a gradient
     assert torch.allclose(metrics, om, rtol=2e-5, atol=1e-6)
     none = run(c, None)                                        # horizons=None: all of them
     for x, y in zip(none, (loss, metrics, dp, dt)):
