@@ -38,6 +38,7 @@ int step_raise_lds_once(const void* kernel, int bytes, const char* what);      /
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
@@ -69,6 +70,30 @@ __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+// The same sums without the LDS pipe: __shfl_xor lowers to ds_bpermute_b32 (LDS latency, six of them dependent per wave_sum), a DPP
+// operand is part of a full-rate vector add.  row_sum_fast: four row shifts (lanes shifted in from outside a 16-lane row read 0), after
+// which lane 15 of every row holds its row's sum -- only that lane does.  wave_sum_fast: two row broadcasts more (lane 15 of rows 0 / 2
+// into rows 1 / 3, lane 31 into rows 2 and 3) leave the total in lane 63, which is returned to every lane through a scalar register.
+// The summation tree is fixed, so results are deterministic, but it is not wave_sum's tree: the two differ in the last bits.
+// Every call site must be reached by ALL 64 lanes of the wave (an inactive lane contributes whatever its register holds, and
+// v_readlane of lane 63 needs no active lane but a defined value): call them outside `if (t < T)` bodies, with 0 in idle lanes.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_add(float v) {
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
+}
+__device__ __forceinline__ float row_sum_fast(float v) {
+    v = dpp_add<0x111, 0xf>(v);      // row_shr:1
+    v = dpp_add<0x112, 0xf>(v);      // row_shr:2
+    v = dpp_add<0x114, 0xf>(v);      // row_shr:4
+    v = dpp_add<0x118, 0xf>(v);      // row_shr:8
+    return v;
+}
+__device__ __forceinline__ float wave_sum_fast(float v) {
+    v = row_sum_fast(v);
+    v = dpp_add<0x142, 0xa>(v);      // row_bcast:15 into rows 1 and 3
+    v = dpp_add<0x143, 0xc>(v);      // row_bcast:31 into rows 2 and 3
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
 }
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll

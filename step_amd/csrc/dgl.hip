@@ -529,7 +529,7 @@ __global__ __launch_bounds__(256) void edge_bwd_row_kernel(const float* __restri
     if (tid < EMB) { sr[tid] = rcv[(long)i * EMB + tid]; sw[tid] = wcat[tid] - wcat[EMB + tid]; }
     float tot = 0.f;
     for (int j = tid; j < N; j += 256) { const float d = dz[(long)i * N + j]; sdz[j] = d; tot += d; }
-    tot = wave_sum(tot);
+    tot = wave_sum_fast(tot);
     if (lane == 0) red[wave] = tot;
     __syncthreads();
     // FIVE features per wave at a time (25 features per wave = five rounds; round 6): a -> drcv, h -> dwcat (sum dz * hid).  With one feature
@@ -572,9 +572,7 @@ __global__ __launch_bounds__(256) void edge_bwd_row_kernel(const float* __restri
             }
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-            for (int u = 0; u < FB; ++u) { a[u] += __shfl_xor(a[u], o, 64); h[u] += __shfl_xor(h[u], o, 64); }
+        for (int u = 0; u < FB; ++u) { a[u] = wave_sum_fast(a[u]); h[u] = wave_sum_fast(h[u]); }     // (ten independent chains, in registers)
         if (lane == 0) {
 #pragma unroll
             for (int u = 0; u < FB; ++u) { ra[f0 + u] = a[u]; rh[f0 + u] = h[u]; }
@@ -711,8 +709,11 @@ __global__ __launch_bounds__(256) void fc_unpermute_kernel(const float* __restri
                                                            const float* __restrict__ st2, const float* __restrict__ colsum,
                                                            float* __restrict__ dfc_w, float* __restrict__ dots_o, int T2, int overwrite) {
     // one thread = one time step of one output row: its 64-byte row of G, 16 coalesced loads of fc_w and of the gradient
-    __shared__ float red[4][32];
-    const int o = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x, tid = threadIdx.x;
+    // the 32 BatchNorm2 sums of a workgroup: in-register sums over the 16 lanes of a DPP row (row_sum_fast), the 16 row sums of each through
+    // 2 KB of LDS -- 32 six-shuffle wave sums per thread were 192 LDS-pipe instructions to move 192 bytes; handing every thread's 32 terms
+    // to LDS instead (32 KB per workgroup) cost residency and was slower than the shuffles, 80 against 57 us
+    __shared__ float red[16][32];
+    const int o = blockIdx.y, t = blockIdx.x * 256 + threadIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float cso = colsum[o];
     float d[32];
 #pragma unroll
@@ -732,11 +733,16 @@ __global__ __launch_bounds__(256) void fc_unpermute_kernel(const float* __restri
     }
 #pragma unroll
     for (int i = 0; i < 32; ++i) {
-        const float v = wave_sum(d[i]);
-        if ((tid & 63) == 0) red[tid >> 6][i] = v;
+        const float v = row_sum_fast(d[i]);
+        if ((lane & 15) == 15) red[4 * wave + (lane >> 4)][i] = v;
     }
     __syncthreads();
-    if (tid < 32) atomicAdd(&dots_o[o * 32 + tid], red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid]);
+    if (tid < 32) {
+        float v = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v += red[r][tid];
+        atomicAdd(&dots_o[o * 32 + tid], v);
+    }
 }
 __global__ void dots_reduce_kernel(const float* __restrict__ dots_o, float* __restrict__ dots) {
     const int i = threadIdx.x;

@@ -442,68 +442,121 @@ __device__ __forceinline__ float bf16lo(uint32_t w) { return __uint_as_float(w <
 __device__ __forceinline__ float bf16hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
 
 // conv1 (1 -> 8 channels, 10 taps, valid) + ReLU on the f32 series -> a1h, BatchNorm1 partial sums (from the f32 values, columns
-// < stat_limit only: the rest is halo of a time slice).  4 consecutive time steps per thread.
+// < stat_limit only: the rest is halo of a time slice).
+//
+// A workgroup covers C1F_SPAN = 4096 time steps, a wave 1024, in two halves of 512: in a half, a lane owns C1F_RUN = 8 consecutive steps
+// (a sliding window of 17 series values in registers), so a half's 512 rows of a1h leave as 8 fully contiguous 1 KB stores per wave
+// after a transpose through a wave-private LDS image.  The 80 weights and 8 biases are wave-uniform scalar loads (two channels at a
+// time), an output is still bias first, then taps 0..9 in order (every one a fused multiply-add now: the compiler used to contract some
+// and split others), ReLU, round to bf16, statistics from the f32 values, and the 16 BatchNorm sums are kept
+// per thread over its 2 x 8 steps and reduced once per workgroup: through LDS across the threads, then one wave_sum_fast per sum.  (With
+// 4 steps per thread and 16 six-shuffle wave sums per thread the kernel issued three times the instructions of its arithmetic.)
+constexpr int C1F_RUN = 8, C1F_HALF = 64 * C1F_RUN, C1F_WAVE = 2 * C1F_HALF, C1F_SPAN = 4 * C1F_WAVE;
+constexpr int C1F_ROW = C1F_RUN + 1;                                   // uint4 per lane of the transpose image (one of padding)
+__device__ __forceinline__ int c1f_xi(int i) { return i + ((i >> 6) << 2); }          // 16 bytes of padding per 64 series values
 __global__ __launch_bounds__(256) void conv1_fwd_cl_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                            const float* __restrict__ b, uint4* __restrict__ a1h,
                                                            float* __restrict__ partial, int T, int stat_limit) {
-    __shared__ float ws[KW][C1_];
-    __shared__ float red[4][2 * C1_];
-    __shared__ __attribute__((aligned(16))) float xs[1024 + 16];
-    const int tid = threadIdx.x, n = blockIdx.y, T1 = T - (KW - 1);
-    if (tid < KW * C1_) ws[tid / C1_][tid % C1_] = w[(tid % C1_) * KW + tid / C1_];
-    // the workgroup's 1024 + 9 series values through LDS: coalesced dword loads (a series row of odd length has no 16-byte alignment),
-    // then four aligned 16-byte LDS reads per thread -- instead of 13 stride-16-byte global loads per thread (22 % of the HBM rate)
+    // one buffer, three lives: the series window [c1f_xi(4096 + 16)] f32, the transpose images [4 waves][64 * C1F_ROW] uint4, the
+    // statistics [16][256] f32
+    __shared__ uint4 buf[4 * 64 * C1F_ROW];
+    static_assert(sizeof(uint4) * 4 * 64 * C1F_ROW >= sizeof(float) * (C1F_SPAN + 16 + ((C1F_SPAN + 16) >> 6) * 4 + 4), "series window fits");
+    static_assert(sizeof(uint4) * 4 * 64 * C1F_ROW >= sizeof(float) * 2 * C1_ * 256, "statistics fit");
+    float* xs = (float*)buf;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = blockIdx.y, T1 = T - (KW - 1);
+    const int tb = blockIdx.x * C1F_SPAN;
+    // the workgroup's 4096 + 9 series values through LDS: coalesced dword loads (a series row of odd length has no 16-byte alignment),
+    // then aligned 16-byte LDS reads (lane stride 32 bytes: the padding keeps 16 consecutive lanes on distinct banks)
+    // All 17 loads of a thread are issued before the first is waited for: the index is clamped into the row instead of branched on (as a
+    // loop of guarded loads this was 17 dependent memory round trips per workgroup, which bounded the kernel next to the encoder).
     {
-        const int tb = blockIdx.x * 1024;
+        constexpr int NLD = (C1F_SPAN + 16 + 255) / 256;
         const float* xr = x + (long)n * T + tb;
-        for (int i = tid; i < 1024 + 16; i += 256) xs[i] = tb + i < T ? xr[i] : 0.f;
-    }
-    __syncthreads();
-    const int t0 = (blockIdx.x * 256 + tid) * 4;
-    float s1[C1_], s2[C1_];
+        const int last = T - 1 - tb;                        // >= 9: a workgroup starts below T - 9
+        float r[NLD];
 #pragma unroll
-    for (int c = 0; c < C1_; ++c) { s1[c] = 0.f; s2[c] = 0.f; }
-    if (t0 < T1) {
-        float xv[16];
+        for (int q = 0; q < NLD; ++q) r[q] = xr[min(min(tid + 256 * q, C1F_SPAN + 15), last)];
 #pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-            const float4 v4 = *(const float4*)(xs + 4 * tid + 4 * q4);
-            xv[4 * q4] = v4.x; xv[4 * q4 + 1] = v4.y; xv[4 * q4 + 2] = v4.z; xv[4 * q4 + 3] = v4.w;
-        }
-        float acc[4][C1_];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int c = 0; c < C1_; ++c) acc[j][c] = b[c];
-#pragma unroll
-        for (int k = 0; k < KW; ++k)
-#pragma unroll
-            for (int c = 0; c < C1_; ++c) {
-                const float wv = ws[k][c];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[j][c] += wv * xv[k + j];
-            }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (t0 + j >= T1) break;
-            float v[C1_];
-#pragma unroll
-            for (int c = 0; c < C1_; ++c) {
-                v[c] = fmaxf(acc[j][c], 0.f);
-                if (t0 + j < stat_limit) { s1[c] += v[c]; s2[c] += v[c] * v[c]; }
-            }
-            a1h[(long)n * T1 + t0 + j] = make_uint4(cvt2(v[0], v[1]), cvt2(v[2], v[3]), cvt2(v[4], v[5]), cvt2(v[6], v[7]));
+        for (int q = 0; q < NLD; ++q) {
+            const int i = tid + 256 * q;
+            if (i < C1F_SPAN + 16) xs[c1f_xi(i)] = i <= last ? r[q] : 0.f;
         }
     }
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int c = 0; c < C1_; ++c) {
-        const float a = wave_sum(s1[c]), q = wave_sum(s2[c]);
-        if (lane == 0) { red[wave][c] = a; red[wave][C1_ + c] = q; }
-    }
     __syncthreads();
-    if (tid < 2 * C1_)
-        partial[((long)blockIdx.y * gridDim.x + blockIdx.x) * (2 * C1_) + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    float xv[2][C1F_RUN + 12];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int q4 = 0; q4 < (C1F_RUN + 12) / 4; ++q4) {
+            const float4 v4 = *(const float4*)(xs + c1f_xi(wave * C1F_WAVE + h * C1F_HALF + C1F_RUN * lane + 4 * q4));
+            xv[h][4 * q4] = v4.x; xv[h][4 * q4 + 1] = v4.y; xv[h][4 * q4 + 2] = v4.z; xv[h][4 * q4 + 3] = v4.w;
+        }
+    __syncthreads();                                       // the window is in registers: buf becomes the transpose images
+    f32x2 s1[C1_ / 2], s2[C1_ / 2];                        // channel pairs
+#pragma unroll
+    for (int cp = 0; cp < C1_ / 2; ++cp) { s1[cp] = f32x2{0.f, 0.f}; s2[cp] = f32x2{0.f, 0.f}; }
+    const int slim = stat_limit < T1 ? stat_limit : T1;
+    uint4* tr = buf + wave * (64 * C1F_ROW);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int tw = tb + wave * C1F_WAVE + h * C1F_HALF;          // first step of this wave's half (wave-uniform)
+        const bool act = tw < T1;
+        if (act) {
+            const int t0 = tw + C1F_RUN * lane;
+            uint32_t o[C1F_RUN][C1_ / 2];
+#pragma unroll
+            for (int cp = 0; cp < C1_ / 2; ++cp) {
+                // two channels per packed multiply-add (v_pk_fma_f32): the weight pair is wave-uniform, the series value is shared
+                const int c0 = 2 * cp, c1 = c0 + 1;
+                f32x2 wv[KW];
+#pragma unroll
+                for (int k = 0; k < KW; ++k) wv[k] = f32x2{w[c0 * KW + k], w[c1 * KW + k]};
+                const f32x2 bv = {b[c0], b[c1]};
+#pragma unroll
+                for (int j = 0; j < C1F_RUN; ++j) {
+                    f32x2 a = bv;
+#pragma unroll
+                    for (int k = 0; k < KW; ++k) a = __builtin_elementwise_fma(wv[k], f32x2{xv[h][k + j], xv[h][k + j]}, a);
+                    const float v0 = fmaxf(a[0], 0.f), v1 = fmaxf(a[1], 0.f);
+                    const bool in = t0 + j < slim;
+                    const f32x2 vm = {in ? v0 : 0.f, in ? v1 : 0.f};
+                    s1[cp] += vm;
+                    s2[cp] = __builtin_elementwise_fma(vm, vm, s2[cp]);
+                    o[j][cp] = cvt2(v0, v1);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < C1F_RUN; ++j) tr[lane * C1F_ROW + j] = make_uint4(o[j][0], o[j][1], o[j][2], o[j][3]);
+        }
+        __syncthreads();
+        if (act) {
+            uint4 rows[C1F_RUN];
+#pragma unroll
+            for (int i = 0; i < C1F_RUN; ++i) {
+                const int s = i * 64 + lane;                         // step within the half: 64 consecutive rows per store
+                rows[i] = tr[(s / C1F_RUN) * C1F_ROW + s % C1F_RUN];
+            }
+#pragma unroll
+            for (int i = 0; i < C1F_RUN; ++i) {
+                const int s = i * 64 + lane;
+                if (tw + s < T1) a1h[(long)n * T1 + tw + s] = rows[i];
+            }
+        }
+        __syncthreads();
+    }
+    // statistics: [sum | sum of squares][channel] of every thread through LDS, four of the 16 sums per wave
+    float* red = (float*)buf;
+#pragma unroll
+    for (int c = 0; c < C1_; ++c) { red[c * 256 + tid] = s1[c >> 1][c & 1]; red[(C1_ + c) * 256 + tid] = s2[c >> 1][c & 1]; }
+    __syncthreads();
+    float* prow = partial + ((long)blockIdx.y * gridDim.x + blockIdx.x) * (2 * C1_);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int v = 4 * wave + u;
+        const float* r = red + v * 256 + lane;
+        const float tot = wave_sum_fast((r[0] + r[64]) + (r[128] + r[192]));
+        if (lane == 0) prow[v] = tot;
+    }
 }
 
 // conv2's weights with BatchNorm1's scale folded in, as the MFMA operand fragments of the forward (3 x 64 lanes) and of the data
@@ -543,9 +596,18 @@ __global__ __launch_bounds__(256) void conv2_fwd_cl_kernel(const uint4* __restri
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = blockIdx.y;
     const int T2 = T1 - (KW - 1), t0 = blockIdx.x * FW_TT;
     const int ln = lane & 15, q = lane >> 4;
-    for (int tt = tid; tt < FW_TT + 16; tt += 256) {
-        const int t = t0 + tt;
-        xs[tt] = t < T1 ? a1h[(long)n * T1 + t] : make_uint4(0u, 0u, 0u, 0u);
+    // the five row loads of a thread in flight together (index clamped into the node's rows, not branched on: as a loop of guarded
+    // loads they were five dependent memory round trips before the first product)
+    {
+        constexpr int NLD = (FW_TT + 16 + 255) / 256;
+        uint4 r[NLD];
+#pragma unroll
+        for (int u = 0; u < NLD; ++u) r[u] = a1h[(long)n * T1 + min(t0 + min(tid + 256 * u, FW_TT + 15), T1 - 1)];
+#pragma unroll
+        for (int u = 0; u < NLD; ++u) {
+            const int tt = tid + 256 * u;
+            if (tt < FW_TT + 16) xs[tt] = t0 + tt < T1 ? r[u] : make_uint4(0u, 0u, 0u, 0u);
+        }
     }
     bf16x8 wf[3];
 #pragma unroll
@@ -571,9 +633,8 @@ __global__ __launch_bounds__(256) void conv2_fwd_cl_kernel(const uint4* __restri
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) { s1[e] += __shfl_xor(s1[e], o, 64); s2[e] += __shfl_xor(s2[e], o, 64); }
-        if (ln == 0) { red[wave][4 * q + e] = s1[e]; red[wave][CO + 4 * q + e] = s2[e]; }
+        const float a = row_sum_fast(s1[e]), b2 = row_sum_fast(s2[e]);      // the 16 lanes of a q are one DPP row: its sum is in lane 15
+        if (ln == 15) { red[wave][4 * q + e] = a; red[wave][CO + 4 * q + e] = b2; }
     }
     __syncthreads();
     if (tid < 2 * CO)
@@ -599,11 +660,25 @@ __global__ __launch_bounds__(256) void conv2_dgrad_cl_kernel(const uint4* __rest
             xall[i] = t < T1 ? a1h[((long)n * T1 + t) * 2 + q] : make_uint2(0u, 0u);
         }
     }
-    for (int tt = tid; tt < FW_TT + 16; tt += 256) {
-        const int t = t0 - (KW - 1) + tt;
-        const bool ok = t >= 0 && t < T2;
-        zs[tt][0] = ok ? dz2h[((long)n * T2 + t) * 2] : make_uint4(0u, 0u, 0u, 0u);
-        zs[tt][1] = ok ? dz2h[((long)n * T2 + t) * 2 + 1] : make_uint4(0u, 0u, 0u, 0u);
+    // the ten row loads of a thread in flight together (index clamped into the node's rows, not branched on; see conv2_fwd_cl_kernel)
+    {
+        constexpr int NLD = (FW_TT + 16 + 255) / 256;
+        uint4 r0[NLD], r1[NLD];
+#pragma unroll
+        for (int u = 0; u < NLD; ++u) {
+            const int t = max(min(t0 - (KW - 1) + min(tid + 256 * u, FW_TT + 15), T2 - 1), 0);
+            r0[u] = dz2h[((long)n * T2 + t) * 2];
+            r1[u] = dz2h[((long)n * T2 + t) * 2 + 1];
+        }
+#pragma unroll
+        for (int u = 0; u < NLD; ++u) {
+            const int tt = tid + 256 * u, t = t0 - (KW - 1) + tt;
+            const bool ok = t >= 0 && t < T2;
+            if (tt < FW_TT + 16) {
+                zs[tt][0] = ok ? r0[u] : make_uint4(0u, 0u, 0u, 0u);
+                zs[tt][1] = ok ? r1[u] : make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
     }
     bf16x8 wf[5];
 #pragma unroll
@@ -720,7 +795,7 @@ __global__ __launch_bounds__(256) void conv2_wgrad_cl_kernel(const uint4* __rest
     }
 #pragma unroll
     for (int co = 0; co < CO; ++co) {
-        const float sm = wave_sum(bsum[co]);
+        const float sm = wave_sum_fast(bsum[co]);
         if (lane == 0) redb[wave][co] = sm;
     }
     __syncthreads();
@@ -802,7 +877,7 @@ __global__ __launch_bounds__(256) void conv1_wgrad_cl_kernel(const uint4* __rest
     }
 #pragma unroll
     for (int co = 0; co < C1; ++co) {
-        const float sm = wave_sum(bsum[co]);
+        const float sm = wave_sum_fast(bsum[co]);
         if (lane == 0) redb[wave][co] = sm;
     }
     __syncthreads();
@@ -893,7 +968,7 @@ int dgl_conv1_wgrad_mfma(const float* dz, const float* x, float* scratch, float*
 int dgl_conv1_fwd_cl(const float* x, const float* w, const float* b, void* a1h, float* partial, int N, int T, int stat_limit, int* nblk,
                      hipStream_t st) {
     const int T1 = T - (KW - 1);
-    dim3 grid(cdiv(T1, 1024), N);
+    dim3 grid(cdiv(T1, C1F_SPAN), N);           // (at most as many partial rows as the 1024-step tiles the work buffer is sized for)
     conv1_fwd_cl_kernel<<<grid, 256, 0, st>>>(x, w, b, (uint4*)a1h, partial, T, stat_limit);
     STEP_LAUNCH_CHECK("conv1_fwd_cl");
     *nblk = grid.x * grid.y;
