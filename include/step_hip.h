@@ -222,6 +222,12 @@ int step_dgl_edges_forward(const float* g, int N, int B, const StepDglParams* p,
 int step_dgl_edges_backward(const float* g, int N, int B, const StepDglParams* p, const float* saved,
                             const float* dtheta, const float* dadj, float temperature, float* work,
                             const StepDglParams* grads, float* dg, void* aux_stream, void* stream);
+/* The same backward with dg_accumulate (0 | 1): 1 makes the [N,100] epilogue ADD into dg instead of storing it (the tile store reads dg
+ * first; one writer per element, no atomics).  Gradient accumulation sums dg over the micro-batches of a group here and runs
+ * step_dgl_global_backward_phase, which is linear in dg, once per group.  0 is step_dgl_edges_backward. */
+int step_dgl_edges_backward_acc(const float* g, int N, int B, const StepDglParams* p, const float* saved,
+                                const float* dtheta, const float* dadj, float temperature, float* work,
+                                const StepDglParams* grads, float* dg, int dg_accumulate, void* aux_stream, void* stream);
 
 /* ---------------------------------------------------------------- GraphWaveNet backbone ----
  * Device pointers named after the reference state_dict keys of `backend.*`

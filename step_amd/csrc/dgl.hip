@@ -1163,10 +1163,30 @@ extern "C" int step_dgl_edges_forward_dyn(const float* g, int N, int B, const St
 // work: dz [N*N] | drcv [N][EMB] | dsndT [EMB][N]
 extern "C" long step_dgl_edges_work_floats(int N) { return (long)N * N + 2L * N * EMB; }
 
+static int dgl_edges_backward_impl(const float* g, int N, int B, const StepDglParams* p, const float* saved, const float* dtheta,
+                                   const float* dadj, float temperature, float* work, const StepDglParams* grads, float* dg,
+                                   int dg_accumulate, void* aux_stream, void* stream);
+
 extern "C" int step_dgl_edges_backward(const float* g, int N, int B, const StepDglParams* p, const float* saved,
                                        const float* dtheta, const float* dadj, float temperature, float* work,
                                        const StepDglParams* grads, float* dg, void* aux_stream, void* stream) {
     STEP_REQUIRE(g && p && saved && work && grads && dg && N > 0 && B > 0, "dgl_edges_backward: bad arguments");
+    return dgl_edges_backward_impl(g, N, B, p, saved, dtheta, dadj, temperature, work, grads, dg, 0, aux_stream, stream);
+}
+
+// step_dgl_edges_backward whose [N, 100] epilogue ADDS into dg when dg_accumulate != 0 (gradient accumulation: the graph learner's global
+// backward is linear in dg, so a group of micro-batches sums dg here and runs that backward once); dg_accumulate == 0 stores, as above
+extern "C" int step_dgl_edges_backward_acc(const float* g, int N, int B, const StepDglParams* p, const float* saved,
+                                           const float* dtheta, const float* dadj, float temperature, float* work,
+                                           const StepDglParams* grads, float* dg, int dg_accumulate, void* aux_stream, void* stream) {
+    STEP_REQUIRE(g && p && saved && work && grads && dg && N > 0 && B > 0 && (dg_accumulate == 0 || dg_accumulate == 1),
+                 "dgl_edges_backward_acc: bad arguments");
+    return dgl_edges_backward_impl(g, N, B, p, saved, dtheta, dadj, temperature, work, grads, dg, dg_accumulate, aux_stream, stream);
+}
+
+static int dgl_edges_backward_impl(const float* g, int N, int B, const StepDglParams* p, const float* saved, const float* dtheta,
+                                   const float* dadj, float temperature, float* work, const StepDglParams* grads, float* dg,
+                                   int dg_accumulate, void* aux_stream, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     AuxLane lane(st, (hipStream_t)aux_stream);
     const float* sndT = saved;
@@ -1192,6 +1212,7 @@ extern "C" int step_dgl_edges_backward(const float* g, int N, int B, const StepD
     STEP_LAUNCH_CHECK("edge_bwd_col");
     // dg = drcv @ W[:, 100:] + dsnd @ W[:, :100]
     StepGemm g1 = gemm_desc(N, EMB, EMB, drcv, EMB, 1, p->fc_out_w + EMB, 2 * EMB, 1, dg, EMB);
+    g1.accumulate = dg_accumulate ? 1 : 0;          // (the tile's store reads dg first: one writer per element, no atomics)
     STEP_TRY(step_gemm_launch(g1, st));
     StepGemm g2 = gemm_desc(N, EMB, EMB, dsndT, 1, N, p->fc_out_w, 2 * EMB, 1, dg, EMB);
     g2.accumulate = 1;

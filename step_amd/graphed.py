@@ -41,6 +41,9 @@ class GraphedTrainStep:
             raise TypeError("GraphedTrainStep drives step_amd.optim.FusedAdamClip (its step count and learning rate live on the device)")
         if model._process_group is not None:
             raise RuntimeError("GraphedTrainStep is single-process: the data-parallel collectives are not captured")
+        if getattr(model, "_grad_accum", 1) != 1:
+            raise RuntimeError(f"GraphedTrainStep captures one backward per optimizer step: the model is set to accumulate "
+                               f"{model._grad_accum} micro-batches (set_grad_accumulation(1) first)")
         hist, long_hist, fut = example_batch
         if not hist.is_cuda:
             raise RuntimeError("step_amd runs only on an AMD GPU: libstep_hip has no CPU fallback")

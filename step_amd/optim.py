@@ -7,9 +7,11 @@ rule as ``torch.optim.Adam`` (L2 weight decay folded into the gradient, bias-cor
 after the square root) preceded by ``torch.nn.utils.clip_grad_norm_``.  Parameters that receive no gradient
 (the reference leaves them at ``grad=None``, so torch's Adam skips them) are not part of the flat buffer.
 
-It consumes the flat gradient buffer of the LAST native backward (``model._flat_grad``): one backward per ``step()``, as in the
-reference's loop.  With gradient accumulation over several backwards use ``torch.optim.Adam`` on ``model.parameters()``
-(``bench.py --torch-optim``), which reads the accumulated ``.grad`` tensors.
+It consumes the flat gradient buffer of the native backward (``model._flat_grad``): one backward per ``step()``, as in the
+reference's loop -- or, after ``model.set_grad_accumulation(k)``, exactly ``k`` backwards whose gradients the native backward summed
+in that buffer (the step count, bias correction and a scheduler advance per ``step()``, not per micro-batch).  Any other
+accumulation over several backwards needs ``torch.optim.Adam`` on ``model.parameters()`` (``bench.py --torch-optim``), which reads
+the accumulated ``.grad`` tensors.
 
 Checkpoints: ``state_dict()`` / ``load_state_dict()`` speak ``torch.optim.Adam``'s format (one ``{"step", "exp_avg", "exp_avg_sq"}``
 entry per parameter, indexed by the parameter's POSITION in the sequence ``params``), so a checkpoint written around either optimizer
@@ -184,7 +186,13 @@ class FusedAdamClip(torch.optim.Optimizer):
         g = self.model._flat_grad
         if g is None:
             raise RuntimeError("FusedAdamClip.step(): no native backward has run since zero_grad()")
-        if self.model._backward_count != 1:
+        k = getattr(self.model, "_grad_accum", 1)
+        if k > 1 and self.dyn is not None:
+            raise RuntimeError("FusedAdamClip.step(): gradient accumulation (k > 1) is not available while a GraphedTrainStep drives this optimizer")
+        if k > 1 and self.model._backward_count != k:
+            raise RuntimeError(f"FusedAdamClip.step(): {self.model._backward_count} native backwards since zero_grad(), the model accumulates "
+                               f"{k} per step (set_grad_accumulation): the flat gradient buffer holds the sum of an unfinished group")
+        if k == 1 and self.model._backward_count != 1:
             raise RuntimeError(f"FusedAdamClip.step(): {self.model._backward_count} native backwards since zero_grad() -- the flat gradient buffer "
                                "holds the last one only; accumulate with torch.optim.Adam on model.parameters() instead")
         if self.flat is not self.model._flat_param or g.numel() != self.flat.numel():

@@ -332,7 +332,7 @@ class _Deferred:
 
 def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, encoder_workgroups=None, native_metrics=True,
                   eval_cache_bytes=0, native_tail=False, native_pretrain=False, native_data_parallel=False, replica_check=True,
-                  native_eval=False, eval_batch_size=None):
+                  native_eval=False, eval_batch_size=None, accumulate=1):
     """-> subclass of ``base`` (the reference's ``STEPRunner``, or any ``BaseTimeSeriesForecastingRunner``) for ``CFG.RUNNER``.
     ``encoder_workgroups``: compute units of the persistent encoder launch next to the step (None: 160 at 307 nodes / 336 tokens, the
     measured optimum of config C2; 0: one workgroup per sequence) -- only used while batches are prefetched.
@@ -378,7 +378,20 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
     loader with an integer ``batch_size`` -- ignored otherwise, and never applied to a ``TSFormer``'s loaders (a pre-training forward
     draws one mask).  Off by default (None) because it is not the same pass: the graph learner samples in eval mode too, its Gumbel
     noise is a function of the forward count and the position in the batch, so a coalesced pass draws other noise than the uncoalesced
-    one -- as another seed would."""
+    one -- as another seed would.
+    ``accumulate``: ``k`` iterations per optimizer step (default 1: easytorch's ``backward`` as it is).  Fifteen of the reference's
+    sixteen ``step/*.py`` configs set ``CFG.GPU_NUM = 2`` with a per-process batch size: on one card that update is ``accumulate=2``.
+    Groups are runs of ``k`` consecutive iterations of an epoch, the last one of an epoch possibly shorter (size ``s``).  At the start
+    of a group ``train_iters`` calls ``optim.zero_grad()`` and the module's ``set_grad_accumulation(s)``; ``backward(loss)`` runs
+    ``(loss / s).backward()`` and, after the group's last iteration, ``optim.step()`` -- the clip stays inside the fused pass, the
+    scheduler and the step count advance per optimizer step, the meters stay per iteration.  It needs the fused optimizer:
+    ``init_training`` raises ``RuntimeError`` when ``accumulate > 1`` and ``FusedAdamClip`` was not swapped in (another optimizer, a
+    module still wrapped, not a native module on a GPU) rather than train with another effective batch size.  Works with
+    ``native_tail``, ``native_pretrain`` and ``native_data_parallel`` (collectives on a group's last backward only)."""
+    import operator
+    if isinstance(accumulate, (bool, float)) or operator.index(accumulate) < 1:
+        raise ValueError(f"native_runner: accumulate must be an integer >= 1, got {accumulate!r}")
+    accumulate = operator.index(accumulate)
 
     class NativeRunner(base):
         native_hooks = True
@@ -390,6 +403,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             self._metric_cache = None
             self._dp_acting = False          # native_data_parallel took the module out of its DistributedDataParallel wrap
             self._val_metrics = None          # native_eval: (what it was built for, the validation pass's EvalMetrics)
+            self._group_size, self._group_pos = 1, 0          # accumulate: size of the open group, iterations of it that ran backward
 
         # ---------------------------------------------------------------- loaders
         def _lookahead(self, loader, on):
@@ -504,6 +518,15 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             model = _unwrap(self.model)
             opt = getattr(self, "optim", None)
             pretrain = self._pretrain_module() is not None
+            self._swap_optimizer(cfg, model, opt, pretrain)
+            from .optim import FusedAdamClip
+            if accumulate > 1 and not isinstance(self.optim, FusedAdamClip):
+                raise RuntimeError(f"step_amd.runner: accumulate={accumulate} needs the fused optimizer, which was not swapped in (it takes "
+                                   "fused_optimizer=True, a STEP -- or, with native_pretrain, a pre-training TSFormer -- on a GPU outside "
+                                   "any wrapper, and a plain torch.optim.Adam with one parameter group and a 2-norm clip): training on "
+                                   "with another effective batch size would be silent")
+
+        def _swap_optimizer(self, cfg, model, opt, pretrain):
             if not (fused_optimizer and (isinstance(model, STEP) or pretrain) and model is self.model and type(opt) is torch.optim.Adam
                     and next(model.parameters()).is_cuda):
                 return          # (under a DistributedDataParallel wrap the reducer owns the .grad tensors: torch's optimizer stays)
@@ -526,6 +549,29 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             self.optim, self.clip_grad_param = fused, None          # the clip is part of the fused pass
             del opt, g, sched          # the last references to the replaced Adam (its moments: two copies of the parameters)
 
+        # ---------------------------------------------------------------- gradient accumulation (accumulate=k)
+        def _group_start(self, iter_index):
+            """an iteration that opens a group: the group's size, zero_grad(), and the module is told how many backwards follow"""
+            if iter_index % accumulate != 0:
+                return
+            try:
+                left = len(self.train_data_loader) - int(iter_index)
+            except TypeError:
+                left = accumulate          # (a loader without a length: full groups)
+            s = max(1, min(accumulate, left))
+            self.optim.zero_grad()
+            _unwrap(self.model).set_grad_accumulation(s)
+            self._group_size, self._group_pos = s, 0
+
+        def backward(self, loss):
+            if accumulate == 1:
+                return super().backward(loss)
+            s = self._group_size
+            (loss / s).backward()
+            self._group_pos += 1
+            if self._group_pos == s:
+                self.optim.step()          # (clip_grad_param is None: the clip is part of the fused pass)
+
         # ---------------------------------------------------------------- meters without a device synchronisation per iteration
         def _check_replicas(self, epoch):
             """every rank runs train_iters (validation and its hooks run on rank 0 only): all ranks see the same answer and raise together.
@@ -542,6 +588,8 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
         def train_iters(self, epoch, iter_index, data):
             if self._dp_acting and replica_check and iter_index == 0:
                 self._check_replicas(epoch)
+            if accumulate > 1:
+                self._group_start(iter_index)
             self._deferring, self._metric_cache = defer_meters, None
             try:
                 scaler = self._tail_scaler() if native_tail else None

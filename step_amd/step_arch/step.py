@@ -112,6 +112,8 @@ class _StepFunction(torch.autograd.Function):
         # evaluation cache (STEP.eval_cache_bytes; STEP.forward decided whether it is active for this call): `ec` is the batch's plan,
         # None for a batch without host origins -- which runs as if the cache were off
         ec_on, model._ec_on = model._ec_on, False
+        # gradient accumulation (STEP.set_grad_accumulation): the open group of a training forward that takes gradients; None for k = 1
+        acc_fwd, model._acc_fwd = model._acc_fwd, False
         ec = model._eval_cache_plan(long_hist, N, Lh // 12, dev) if ec_on else None
         # Everything up to the GraphWaveNet head is independent of the (frozen) TSFormer: the DGL's global feature, the edge
         # logits, the Gumbel sample and the 8 WaveNet layers only need the train series, the short history and the weights.
@@ -140,8 +142,15 @@ class _StepFunction(torch.autograd.Function):
         g_key = model._eval_g_key(bf, N, Ttr) if ec_on else None
         g = model._eval_g_lookup(g_key) if g_key is not None else None
         g_kept = g is not None
+        grp = model._group_forward(bf, N, Ttr) if acc_fwd else None
         if g_kept:
             gsaved = gwork = None          # (only a backward reads gsaved; none can follow a forward without gradients)
+        elif grp is not None and grp["fwd"] > 0 and grp["fwd"] < grp["k"]:
+            # a further micro-batch of the open group: the global branch reads the train series and the learner's weights only, which do
+            # not change inside a group -- its forward ran with the group's first micro-batch
+            g, gsaved = grp["kept"]
+            gwork = None
+            g_kept = True
         else:
             gsaved = _f32(L.lib().step_dgl_global_saved_floats(N, Ttr), dev)
             gwork = _f32(L.lib().step_dgl_global_work_floats(N, Ttr, 0), dev)
@@ -205,7 +214,9 @@ class _StepFunction(torch.autograd.Function):
                 with torch.no_grad():
                     # the BatchNorm step counters: one multi-tensor launch instead of ten scalar ones, on this (the second) stream -- on the
                     # main stream it sat between the head and the loss
-                    torch._foreach_add_([m.num_batches_tracked for m in (dgl.bn1, dgl.bn2, dgl.bn3, *list(be.bn)[:8 if model.track_dead_bn7 else 7])], 1)
+                    # (a kept global feature: the learner's BatchNorm layers saw no batch -- once per accumulation group)
+                    torch._foreach_add_([m.num_batches_tracked for m in (*(() if g_kept else (dgl.bn1, dgl.bn2, dgl.bn3)),
+                                                                         *list(be.bn)[:8 if model.track_dead_bn7 else 7])], 1)
 
         # ---- TSFormer (frozen) and the kNN prior graph (no grad): on the main stream, or already in flight on the prefetch stream
         if frozen is None and ec is not None and ec["hit"]:
@@ -250,6 +261,11 @@ class _StepFunction(torch.autograd.Function):
             model._eval_cache_store(ec, frozen, B, N, dev)          # the windows not stored yet (nothing for a batch served from the cache)
         if g_key is not None and not g_kept:
             model._eval_g = (g_key, g)
+        if grp is not None:
+            if grp["fwd"] == 0:
+                grp["kept"] = (g, gsaved)
+            grp["fwd"] += 1
+        ctx.group = grp
         ctx.model = model
         ctx.dims = (B, N, Cin, Ttr, float(drop))
         ctx.held = (hist, enc["last"], g, gsaved, esaved, wsaved)
@@ -272,10 +288,20 @@ class _StepFunction(torch.autograd.Function):
         # the flat gradient buffer: everything in front of the fc weight (gradients accumulate into zeros, 18 MB at PEMS04) is cleared; the fc
         # weight's 87 MB are STORED by the graph learner's backward (STEP_DGL_FRESH_FC_GRAD), neither cleared here nor read there
         fo, fn, _ = layout["items"]["dgl.fc_w"]
-        flat, views, gw_grads, dg_grads = model._grad_buffers(layout, dev)
-        flat[:fo].zero_()
-        if fo + fn < layout["total"]:
-            flat[fo + fn:].zero_()
+        # gradient accumulation: micro-batch `nth` of the group's k (by order of the backwards).  The first one clears as always; the
+        # later ones clear nothing -- every GraphWaveNet / edge kernel adds into what is there -- and only the last runs the graph
+        # learner's global backward (linear in dg, which the edge backward sums over the group) and the data-parallel collectives
+        grp = ctx.group
+        nth, final = (1, True) if grp is None else model._group_backward(grp)
+        if nth == 1:
+            flat, views, gw_grads, dg_grads = model._grad_buffers(layout, dev)
+            flat[:fo].zero_()
+            if fo + fn < layout["total"]:
+                flat[fo + fn:].zero_()
+            if grp is not None:
+                grp["bufs"] = (flat, views, gw_grads, dg_grads)
+        else:
+            flat, views, gw_grads, dg_grads = grp["bufs"]
         bf = {"f32": 0, "bf16": 1}[model.matmul_precision]
         dstruct, bstruct = model._param_structs(bf, full=False)
         dpred = dpred.contiguous().float().view(B, 12, N) if dpred is not None else torch.zeros(B, 12, N, device=dev)
@@ -308,16 +334,26 @@ class _StepFunction(torch.autograd.Function):
                    L.ptr(dpred), ctypes.byref(gw_grads), L.ptr(dadj), int(drop > 0), aux, leaf, st)
             # (wwork / ework stay referenced until the auxiliary stream is joined below: its last leaves still read them)
             ework = _f32(L.lib().step_dgl_edges_work_floats(N), dev)
-            dgv = _f32(N * 100, dev)
             dth = dtheta.contiguous().float() if dtheta is not None else None
-            L.call("step_dgl_edges_backward", L.ptr(g), N, B, ctypes.byref(dstruct), L.ptr(esaved), L.ptr(dth) if dth is not None else None,
-                   L.ptr(dadj), TEMPERATURE, L.ptr(ework), ctypes.byref(dg_grads), L.ptr(dgv), leaf if leaf is not None else aux, st)
-            gwork = _f32(L.lib().step_dgl_global_work_floats(N, Ttr, 1), dev)
+            if grp is None:
+                dgv = _f32(N * 100, dev)
+                L.call("step_dgl_edges_backward", L.ptr(g), N, B, ctypes.byref(dstruct), L.ptr(esaved), L.ptr(dth) if dth is not None else None,
+                       L.ptr(dadj), TEMPERATURE, L.ptr(ework), ctypes.byref(dg_grads), L.ptr(dgv), leaf if leaf is not None else aux, st)
+            else:
+                # the group's one [N,100] buffer: stored by the first micro-batch, added to by the others in the kernel's epilogue
+                if nth == 1:
+                    grp["dg"] = _f32(N * 100, dev)
+                dgv = grp["dg"]
+                L.call("step_dgl_edges_backward_acc", L.ptr(g), N, B, ctypes.byref(dstruct), L.ptr(esaved), L.ptr(dth) if dth is not None else None,
+                       L.ptr(dadj), TEMPERATURE, L.ptr(ework), ctypes.byref(dg_grads), L.ptr(dgv), int(nth > 1), leaf if leaf is not None else aux, st)
+            gwork = _f32(L.lib().step_dgl_global_work_floats(N, Ttr, 1), dev) if final else None
             fo, fn, _ = layout["items"]["dgl.fc_w"]
             assert fo + fn == layout["total"] or fo + ((fn + 3) & ~3) == layout["total"]
             assert layout["norm_slot"] == fo - 4
             sh = dgl._shard
-            if sh is None:
+            if not final:
+                join_aux()          # (same contract on every micro-batch: the next one's kernels add into `flat` behind these leaves)
+            elif sh is None:
                 L.call("step_dgl_global_backward_phase", L.ptr(dgl._series_nt), N, Ttr, ctypes.byref(dstruct), L.ptr(gsaved), L.ptr(dgv),
                        L.ptr(gwork), ctypes.byref(dg_grads), 1 | FRESH, st)
                 pending = model._reduce_begin(flat[fo:fo + fn])          # overlaps with the conv / BatchNorm backward below
@@ -372,7 +408,9 @@ class _StepFunction(torch.autograd.Function):
         model._drop_eval_g()          # the optimizer is about to write the learner's weights through raw pointers
         ctx.held = None
         del views, gw_grads, dg_grads
-        if model.flat_gradients_only:
+        if model.flat_gradients_only or nth > 1:
+            # (a later micro-batch of a group: the .grad tensors autograd adopted from the first one ARE views of `flat` and already hold the
+            #  sum -- a second view would be added onto its own alias)
             # the caller reads model._flat_grad (step_amd.optim.FusedAdamClip does): no per-parameter .grad tensors, no AccumulateGrad work
             return (None, None, None, None) + (None,) * len(layout["order"])
         # FRESH views with no other owner, built on every backward: autograd's AccumulateGrad adopts such a tensor as .grad (an alias of
@@ -492,6 +530,11 @@ class STEP(nn.Module):
         self._eval_cache = None             # eval_cache.FrozenBranchCache
         self._eval_cache_alloc = None       # tests: allocator of the storage chunks (None: device tensors)
         self._eval_g = None                 # (key, g [N, 100]) of the last eval-mode global forward, see _eval_g_key
+        # Gradient accumulation (set_grad_accumulation): k native backwards per optimizer step add into one flat gradient buffer
+        self._grad_accum = 1
+        self._group_open = False            # a training forward that takes gradients has run since zero_grad()
+        self._acc = None                    # the open group for k > 1: counts, the kept (g, gsaved), the gradient buffers, the summed dg
+        self._acc_fwd = False               # forward() -> _StepFunction.forward: this call is a training forward that takes gradients
         self._ec_on = False                 # forward() -> _StepFunction.forward: the cache is active for this call
 
     def load_pre_trained_model(self):
@@ -708,7 +751,97 @@ class STEP(nn.Module):
         self._eval_g = None
 
     def _drop_eval_g(self):
+        """a kernel is about to write (or has written) the learner's weights through raw pointers: nothing computed from them is kept"""
         self._eval_g = None
+        if self._acc is not None and self._acc["bwd"] >= self._acc["k"]:
+            self._acc["kept"] = None          # (the optimizer step that ends the group; a backward inside it changes no weight)
+
+    # ------------------------------------------------------------------ gradient accumulation
+    def set_grad_accumulation(self, k):
+        """``k`` micro-batches per optimizer step (default 1: one backward per ``step()``, nothing changes).  For ``k > 1`` the native
+        backwards of the ``k`` training forwards that follow a ``zero_grad()`` ADD into ``model._flat_grad`` (torch's semantics: scale
+        the loss by ``1 / k`` yourself), in any interleaving of forwards and backwards; ``FusedAdamClip.step()`` then takes exactly ``k``
+        backwards, a ``k + 1``-th raises, ``zero_grad()`` closes the group.  With ``param_grads=True`` the ``.grad`` tensors are views of
+        the flat buffer and hold the sum.
+
+        The graph learner's global branch (conv1 .. bn3) reads the train series and the learner's weights only, never the batch, and
+        its backward is linear in the gradient of its output: a group runs its forward ONCE (first training forward) and its backward
+        ONCE (last backward, on the gradient summed over the group), together with the data-parallel collectives.  Consequently the
+        learner's three BatchNorm layers update running statistics and ``num_batches_tracked`` once per group -- as rank 0 does once
+        per step in the reference's two-GPU recipe -- while the backbone's BatchNorm layers update per micro-batch.  Eval-mode and
+        ``no_grad`` forwards neither use nor disturb the group.  Writing the learner's weights inside a group (``load_state_dict``,
+        ``.to()``, an optimizer step) drops what the group kept: the next training forward without a ``zero_grad()`` raises.
+
+        Not with ``shard_graph_learner=True`` nor with a ``GraphedTrainStep`` attached (``RuntimeError``)."""
+        import operator
+        if isinstance(k, bool) or isinstance(k, float):
+            raise TypeError(f"set_grad_accumulation: k must be an integer >= 1, got {k!r}")
+        try:
+            k = operator.index(k)
+        except TypeError:
+            raise TypeError(f"set_grad_accumulation: k must be an integer >= 1, got {k!r}") from None
+        if k < 1:
+            raise ValueError(f"set_grad_accumulation: k must be >= 1, got {k}")
+        if self._group_open:
+            raise RuntimeError("set_grad_accumulation: an accumulation group is open (a training forward has run since the last "
+                               "zero_grad()): call zero_grad() first")
+        if k > 1:
+            self._refuse_accumulation()
+        self._grad_accum = k
+        self._acc = None
+
+    def _refuse_accumulation(self):
+        if self.discrete_graph_learning._shard is not None:
+            raise RuntimeError("gradient accumulation (k > 1) is not available with a time-sliced graph learner (shard_graph_learner=True): "
+                               "its norm slot and per-slice phases assume one backward per step")
+        if self._dyn is not None:
+            raise RuntimeError("gradient accumulation (k > 1) is not available while a GraphedTrainStep is attached: close() it first")
+
+    def _group_key(self, bf, N, Ttr):
+        """identity of everything the kept (g, gsaved) was computed from: series, precision mode, address and version of the learner's
+        tensors (raw-pointer writers call _drop_eval_g)"""
+        dgl = self.discrete_graph_learning
+        sr = dgl._series_nt
+        return (int(bf), int(N), int(Ttr), sr.data_ptr(), sr._version,
+                tuple((v.data_ptr(), v._version) for n, v in dgl.native_tensors(full=True).items() if not n.endswith(("_rm", "_rv"))))
+
+    def _group_forward(self, bf, N, Ttr):
+        """a training forward that takes gradients: opens the group, or joins the open one.  -> the group (None for k = 1)"""
+        self._group_open = True
+        k = self._grad_accum
+        if k == 1:
+            return None
+        self._refuse_accumulation()
+        grp = self._acc
+        if grp is None:
+            grp = self._acc = {"k": k, "fwd": 0, "bwd": 0, "kept": None, "key": self._group_key(bf, N, Ttr), "bufs": None, "dg": None}
+            return grp
+        if grp["fwd"] == 0:
+            grp["key"] = self._group_key(bf, N, Ttr)          # (the group's first forward raised: this one takes its place)
+            return grp
+        if grp["fwd"] >= k:
+            return grp          # one forward too many: it runs on its own global feature, and its backward raises (_group_backward)
+        if grp["kept"] is None or grp["key"] != self._group_key(bf, N, Ttr):
+            raise RuntimeError("step_amd.STEP: the graph learner's weights (or the precision mode) changed inside an accumulation group "
+                               "(load_state_dict, .to(), an optimizer step): the group's global feature is stale -- call zero_grad() and "
+                               "start the group again")
+        return grp
+
+    def _group_backward(self, grp):
+        """-> (which backward of the group this is, counted from 1; whether it is the last)"""
+        if grp is not self._acc:
+            raise RuntimeError("step_amd.STEP: backward of a forward whose accumulation group was closed by zero_grad()")
+        if grp["bwd"] >= grp["k"]:
+            raise RuntimeError(f"step_amd.STEP: backward {grp['bwd'] + 1} of an accumulation group of {grp['k']} micro-batches")
+        if grp["bwd"] > 0 and grp["bufs"] is None:
+            raise RuntimeError("step_amd.STEP: an earlier backward of this accumulation group failed: call zero_grad() and start the group again")
+        if grp["bwd"] == 0 and not self.flat_gradients_only:
+            tr = self._trainable_list()
+            if any(q.grad is not None for q in (tr[0], tr[len(tr) // 2], tr[-1])):
+                raise RuntimeError("step_amd.STEP: gradient accumulation (k > 1) starts from parameters without .grad tensors (they become "
+                                   "views of the flat gradient buffer): use zero_grad(set_to_none=True)")
+        grp["bwd"] += 1
+        return grp["bwd"], grp["bwd"] == grp["k"]
 
     def _eval_cache_plan(self, long_hist, N, P, dev=None, channel=0):
         """-> {"cache", "keys", "hit", ...} for a batch with host origins, None otherwise.  Compares the cache's tie first and drops a
@@ -1020,6 +1153,8 @@ class STEP(nn.Module):
             super().zero_grad(set_to_none=False)
         self._flat_grad = None
         self._backward_count = 0
+        self._group_open = False
+        self._acc = None
 
     def train(self, mode=True):
         if bool(mode) != self.training and self._prefetched:
@@ -1032,6 +1167,8 @@ class STEP(nn.Module):
         self._zg_params = None
         self._struct_cache, self._bwd_cache, self._trainable_cache = {}, None, None
         self._invalidate_eval_cache()
+        if self._acc is not None:
+            self._acc["kept"] = None          # the weights are about to be re-homed or converted: the open group cannot go on
         out = super()._apply(fn, recurse)
         flat = self._flat_param
         if flat is not None:
@@ -1046,6 +1183,8 @@ class STEP(nn.Module):
         self._zg_params = None
         self._struct_cache, self._bwd_cache, self._trainable_cache = {}, None, None
         self._invalidate_eval_cache()
+        if self._acc is not None:
+            self._acc["kept"] = None          # new weights: the open accumulation group's global feature is stale
         return super().load_state_dict(*a, **kw)
 
     # ------------------------------------------------------------------ forward
@@ -1061,6 +1200,7 @@ class STEP(nn.Module):
             u = None
         params = self._trainable_list()
         self._ec_on = self.eval_cache_bytes > 0 and self._eval_cache_active()
+        self._acc_fwd = self.training and torch.is_grad_enabled()
         pred, theta, adj_knn = _StepFunction.apply(self, history_data, long_history_data, u, *params)
         if epoch is not None:
             gsl_coefficient = 1 / (int(epoch / 6) + 1)

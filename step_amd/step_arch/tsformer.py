@@ -403,7 +403,9 @@ class _PretrainFunction(torch.autograd.Function):
             # forward is rebuilt first -- the fill is a pure function of (seed, p)
             fz["pool"], fz["words"] = model._pt_pool(dr.device, p, seed)
         P_ = {n: prm for n, prm in zip(model._pt_names, model._pt_params())}
-        flat, G = model._pt_grad_buffers()
+        # gradient accumulation (set_grad_accumulation): backward `nth` of the group's k; every kernel below ADDS into G, which is zeroed
+        # for the first one only
+        flat, G, nth, last = model._pt_group_backward()
         dev = dr.device
         dr = dr.contiguous().float().view(S * P, 12)
         pos = P_["positional_encoding.position_embedding"]
@@ -439,9 +441,7 @@ class _PretrainFunction(torch.autograd.Function):
                    L.ptr(G["positional_encoding.position_embedding"]), L.ptr(G["patch_embedding.input_embedding.weight"]),
                    L.ptr(G["patch_embedding.input_embedding.bias"]), st)
             ctx.saved = None
-            model._backward_count += 1
-            model._reduce_flat_grad(flat)          # data parallel: the views returned below then hold the group's mean
-            return (None, None, None, None) + tuple(G[n] for n in model._pt_names)
+            return (None, None, None, None) + model._pt_backward_done(flat, G, nth, last)
         # scatter back to all token positions (zeros at masked ones), dropout, positional and patch embedding
         de = torch.zeros(S * P, 96, device=dev)
         L.call("step_pt_token_scatter", L.ptr(dx), S, P, L.ptr(sv["um"]), Pu, SQRT_D, L.ptr(de), st)
@@ -451,9 +451,7 @@ class _PretrainFunction(torch.autograd.Function):
         patches = sv["series"].view(S * P, 12)
         _linear_bwd(de, patches, None, G["patch_embedding.input_embedding.weight"].view(96, 12), G["patch_embedding.input_embedding.bias"])
         ctx.saved = None
-        model._backward_count += 1
-        model._reduce_flat_grad(flat)
-        return (None, None, None, None) + tuple(G[n] for n in model._pt_names)
+        return (None, None, None, None) + model._pt_backward_done(flat, G, nth, last)
 
 
 _PT_TAIL_WORK = {}
@@ -544,7 +542,10 @@ class TSFormer(nn.Module):
         self._ffn_pack_bufs = None
         self._flat_param = None             # flatten_parameters(): all parameters as views into one buffer (FusedAdamClip)
         self._flat_grad = None
-        self._backward_count = 0            # native backwards since zero_grad() (FusedAdamClip consumes exactly one)
+        self._backward_count = 0            # native backwards since zero_grad() (FusedAdamClip consumes exactly _grad_accum)
+        self._grad_accum = 1                # set_grad_accumulation(k): k pre-training backwards add into one flat gradient buffer
+        self._group_open = False            # a training forward that takes gradients has run since zero_grad()
+        self._acc = None                    # k > 1: the open group's flat buffer, its views and the number of backwards so far
         # enable_native_data_parallel(): the group the pre-training backward averages its flat gradient over
         self._process_group = None
         self._min_world = 1
@@ -818,7 +819,70 @@ class TSFormer(nn.Module):
 
     def zero_grad(self, set_to_none=True):
         self._backward_count = 0
+        self._group_open = False
+        self._acc = None
         super().zero_grad(set_to_none=set_to_none)
+
+    def set_grad_accumulation(self, k):
+        """``k`` pre-training micro-batches per optimizer step (default 1: nothing changes).  For ``k > 1`` the flat gradient buffer
+        lives from the first backward after ``zero_grad()`` to the next ``zero_grad()``: it is zeroed for the first backward, the
+        others add into it (torch's semantics: scale the loss by ``1 / k`` yourself), the ``.grad`` tensors are views of it, and the
+        data-parallel mean is taken on the ``k``-th backward only.  ``FusedAdamClip.step()`` then takes exactly ``k`` backwards; a
+        ``k + 1``-th raises."""
+        import operator
+        if isinstance(k, (bool, float)):
+            raise TypeError(f"set_grad_accumulation: k must be an integer >= 1, got {k!r}")
+        try:
+            k = operator.index(k)
+        except TypeError:
+            raise TypeError(f"set_grad_accumulation: k must be an integer >= 1, got {k!r}") from None
+        if k < 1:
+            raise ValueError(f"set_grad_accumulation: k must be >= 1, got {k}")
+        if self._group_open:
+            raise RuntimeError("set_grad_accumulation: an accumulation group is open (a training forward has run since the last "
+                               "zero_grad()): call zero_grad() first")
+        self._grad_accum = k
+        self._acc = None
+
+    def _pt_group_backward(self):
+        """-> (flat, G, which backward of the group this is (from 1), whether it is the last); k = 1: fresh zeroed buffers, (1, True)"""
+        k = self._grad_accum
+        if k == 1:
+            flat, G = self._pt_grad_buffers()
+            return flat, G, 1, True
+        acc = self._acc
+        prm = self._pt_params()
+        probe = (prm[0], prm[len(prm) // 2], prm[-1])
+        if acc is None:
+            if any(q.grad is not None for q in probe):
+                raise RuntimeError("step_amd.TSFormer: gradient accumulation (k > 1) starts from parameters without .grad tensors (they "
+                                   "become views of the flat gradient buffer): use zero_grad(set_to_none=True)")
+            flat, G = self._pt_grad_buffers()
+            acc = self._acc = {"flat": flat, "G": G, "bwd": 0}
+        elif acc["bwd"] >= k:
+            raise RuntimeError(f"step_amd.TSFormer: backward {acc['bwd'] + 1} of an accumulation group of {k} micro-batches")
+        else:
+            flat = acc["flat"]
+            lo, hi = flat.data_ptr(), flat.data_ptr() + flat.numel() * flat.element_size()
+            if any(q.grad is None or not (lo <= q.grad.data_ptr() < hi) for q in probe):
+                raise RuntimeError("step_amd.TSFormer: a parameter's .grad is no longer a view of the group's flat gradient buffer (replaced "
+                                   "or cleared inside an accumulation group): call zero_grad() and start the group again")
+        acc["bwd"] += 1
+        return acc["flat"], acc["G"], acc["bwd"], acc["bwd"] == k
+
+    def _pt_backward_done(self, flat, G, nth, last):
+        """count the backward, take the data-parallel mean when the group is complete; -> what autograd gets for the parameters"""
+        self._backward_count += 1
+        if last:
+            self._reduce_flat_grad(flat)          # data parallel: the views then hold the group's mean
+        if self._grad_accum == 1:
+            return tuple(G[n] for n in self._pt_names)
+        if nth > 1:
+            # the .grad tensors autograd adopted from the group's first backward ARE views of `flat` and already hold the sum: a second
+            # view would be added onto its own alias
+            return (None,) * len(self._pt_names)
+        # FRESH views with no other owner (the group keeps G): autograd adopts such a tensor as .grad and clones one that is shared
+        return tuple(G[n].view(G[n].shape) for n in self._pt_names)
 
     def _pt_grad_buffers(self):
         prm = self._pt_params()
@@ -928,6 +992,8 @@ class TSFormer(nn.Module):
     def _pretrain_output(self, history_data):
         """-> (r [S, P, 12] the decoder's output, series [S, L], masked indices int32 [Pm] on the device, (B, N, P, Pu))"""
         series, B, N, L = self._pretrain_series(history_data)
+        if self.training and torch.is_grad_enabled():
+            self._group_open = True
         um_list, mk_list = self.mask()
         um = torch.tensor(um_list, dtype=torch.int32, device=series.device)
         mk = torch.tensor(mk_list, dtype=torch.int32, device=series.device)
