@@ -16,11 +16,13 @@ the accumulated ``.grad`` tensors.
 Checkpoints: ``state_dict()`` / ``load_state_dict()`` speak ``torch.optim.Adam``'s format (one ``{"step", "exp_avg", "exp_avg_sq"}``
 entry per parameter, indexed by the parameter's POSITION in the sequence ``params``), so a checkpoint written around either optimizer
 resumes around the other.  The two conversions are the plain functions ``moments_to_state`` / ``state_to_moments`` below (no library,
-no device needed).
+no device needed).  With the graph learner in time slices the flat buffers hold one rank's columns of ``fc.weight``:
+``FusedAdamClip(gathered_state=True)`` cuts a loaded state to them and emits torch's format after ``gather_state()``, a collective.
 """
 import torch
 
 from . import _lib
+from .step_arch.discrete_graph_learning import cut_time_columns, paste_time_columns
 
 
 def flat_items(model):
@@ -52,18 +54,22 @@ def index_flat_items(items, params, names=None):
     return index, label
 
 
-def moments_to_state(index, exp_avg, exp_avg_sq, step):
+def moments_to_state(index, exp_avg, exp_avg_sq, step, gathered=None):
     """flat moment buffers -> the ``"state"`` of ``torch.optim.Adam.state_dict()``: per flat parameter two VIEWS into the buffers (no
     copy, no synchronisation; ``torch.save`` writes the shared storage once) and ``step`` as torch keeps it, a 0-d float32 host tensor
-    of its own.  Empty before the first step, as torch's."""
+    of its own.  Empty before the first step, as torch's.  ``gathered``: ``{position: (exp_avg, exp_avg_sq)}`` in the parameter's
+    full shape for the positions of which the flat buffers hold only this rank's time slice (``FusedAdamClip.gather_state``)."""
     if int(step) == 0:
         return {}
     state = {}
     for i in sorted(index):
         _, off, p = index[i]
         n = p.numel()
-        state[i] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": exp_avg[off:off + n].view(p.shape),
-                    "exp_avg_sq": exp_avg_sq[off:off + n].view(p.shape)}
+        if gathered is not None and i in gathered:
+            m, v = gathered[i]
+        else:
+            m, v = exp_avg[off:off + n].view(p.shape), exp_avg_sq[off:off + n].view(p.shape)
+        state[i] = {"step": torch.tensor(float(step), dtype=torch.float32), "exp_avg": m, "exp_avg_sq": v}
     return state
 
 
@@ -74,10 +80,20 @@ def _step_value(v):
     return int(v)
 
 
-def state_to_moments(index, label, sd, exp_avg, exp_avg_sq):
+def state_to_moments(index, label, sd, exp_avg, exp_avg_sq, sliced=None):
     """``torch.optim.Adam.state_dict()`` -> the flat moment buffers (everything outside the parameters -- padding, spare slots -- is
     left zero); returns the common step count.  Saved parameter ids are mapped to positions the way ``Optimizer.load_state_dict`` does:
-    in the order the groups list them.  Everything is checked before anything is written."""
+    in the order the groups list them.  Everything is checked before anything is written.  ``sliced``: ``{position: (T2, a, b)}`` for
+    the positions of which the flat buffers hold only the time columns [a, b) (``cut_time_columns``): their moments arrive in the
+    parameter's full shape, are checked against it, and this rank's columns are copied."""
+    sliced = sliced or {}
+
+    def extent(i):          # (offset, floats) of position i in the flat buffers
+        _, off, p = index[i]
+        if i in sliced:
+            T2, a, b = sliced[i]
+            return off, p.numel() // T2 * (b - a)
+        return off, p.numel()
     ids = [i for g in sd["param_groups"] for i in g["params"]]
     if len(ids) != len(label):
         raise ValueError(f"FusedAdamClip: the optimizer state was saved around {len(ids)} parameters, this optimizer was given {len(label)}")
@@ -110,15 +126,20 @@ def state_to_moments(index, label, sd, exp_avg, exp_avg_sq):
         exp_avg_sq.zero_()
         return 0
     end = 0          # (the entries may be views of these very buffers -- load_state_dict(state_dict()) -- so only the gaps are zeroed)
-    for _, off, p in sorted(index.values(), key=lambda item: item[1]):
+    for off, n in sorted(extent(i) for i in index):
         exp_avg[end:off].zero_()
         exp_avg_sq[end:off].zero_()
-        end = off + p.numel()
+        end = off + n
     exp_avg[end:].zero_()
     exp_avg_sq[end:].zero_()
     for i, st in entries.items():
-        _, off, p = index[i]
-        n = p.numel()
+        _, _, p = index[i]
+        off, n = extent(i)
+        if i in sliced:
+            T2, a, b = sliced[i]
+            exp_avg[off:off + n].view(p.shape[0], -1).copy_(cut_time_columns(st["exp_avg"].contiguous(), T2, a, b))
+            exp_avg_sq[off:off + n].view(p.shape[0], -1).copy_(cut_time_columns(st["exp_avg_sq"].contiguous(), T2, a, b))
+            continue
         exp_avg[off:off + n].view(p.shape).copy_(st["exp_avg"])
         exp_avg_sq[off:off + n].view(p.shape).copy_(st["exp_avg_sq"])
     return next(iter(steps.values()))
@@ -143,13 +164,24 @@ class FusedAdamClip(torch.optim.Optimizer):
     """A ``torch.optim.Optimizer`` (so ``torch.optim.lr_scheduler.MultiStepLR`` -- the reference's ``CFG.TRAIN.LR_SCHEDULER``,
     step/STEP_PEMS04.py:98-102 -- drives ``param_groups[0]["lr"]`` as usual) whose single parameter is the model's flat buffer."""
 
-    def __init__(self, model, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, param_grads=True, params=None):
+    # a HostFused-style subclass that skips __init__ (tests) is an optimizer without slices
+    gathered_state = False
+    _sliced = None          # {position of fc.weight in params: (T2, a, b)} while ``gathered_state`` acts
+    _staging = None          # what gather_state() left: None, or {position: (exp_avg, exp_avg_sq)} (empty on the other ranks)
+
+    def __init__(self, model, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, param_grads=True, params=None,
+                 gathered_state=False):
         """``param_grads=False`` (STEP only): the native backward leaves the gradients in the flat buffer this optimizer reads and does
         not hand ~100 per-parameter ``.grad`` views to autograd (0.3-0.5 ms of host time per step); ``p.grad`` stays None.
         ``params``: the ordered sequence of Parameters whose POSITIONS are the indices of ``state_dict()`` -- what the
         ``torch.optim.Adam`` this optimizer stands in for holds, or would hold (default: ``list(model.parameters())``).  Every
-        parameter of the flat buffer must be in it (``ValueError``); matching is by identity, which flattening keeps."""
+        parameter of the flat buffer must be in it (``ValueError``); matching is by identity, which flattening keeps.
+        ``gathered_state`` (only with a graph learner in time slices, ignored otherwise): ``state_dict()`` / ``load_state_dict()``
+        speak torch's format there too -- the flat buffer's ``fc.weight`` slice is bound to ``fc.weight``'s position in ``params``,
+        a loaded state's full moments are cut to this rank's columns, and an emitted state takes ``fc.weight``'s full moments from
+        ``gather_state()``, a collective.  Without it a sliced optimizer keeps the flat per-rank format (see ``state_dict``)."""
         self.model = model
+        self.gathered_state = bool(gathered_state)
         if not param_grads and hasattr(model, "flat_gradients_only"):
             model.flat_gradients_only = True
         self.flat = model._flat_param if model._flat_param is not None else model.flatten_parameters()
@@ -168,13 +200,23 @@ class FusedAdamClip(torch.optim.Optimizer):
         return getattr(getattr(self.model, "discrete_graph_learning", None), "_shard", None) is not None
 
     def _bind_params(self, params):
-        """the identity map between positions in ``params`` and the flat buffer (not with a sharded graph learner: see state_dict)"""
-        self._index = self._label = None
+        """the identity map between positions in ``params`` and the flat buffer.  With a sharded graph learner: none (see state_dict)
+        -- or, with ``gathered_state``, the same map with the flat item ``dgl.fc_w`` (this rank's ``fc_weight_slice``) bound to the
+        position and the full shape of ``fc.weight``, which is what ``params`` -- the replaced Adam's list -- holds"""
+        self._index = self._label = self._sliced = self._staging = None
+        items = flat_items(self.model)
         if self._sharded():
-            return
+            if not self.gathered_state:
+                return
+            dgl = self.model.discrete_graph_learning
+            items = [(n, off, dgl.fc.weight if n == "dgl.fc_w" else p) for n, off, p in items]
         params = list(self.model.parameters()) if params is None else list(params)
         names = {id(p): n for n, p in self.model.named_parameters()}
-        self._index, self._label = index_flat_items(flat_items(self.model), params, names)
+        self._index, self._label = index_flat_items(items, params, names)
+        if self._sharded():
+            sh = dgl._shard
+            at = next(i for i, (n, _, _) in self._index.items() if n == "dgl.fc_w")
+            self._sliced = {at: (dgl.train_length - 18, sh["a"], sh["b"])}
 
     def zero_grad(self, set_to_none=True):
         self.model.zero_grad(set_to_none=set_to_none)          # STEP.zero_grad also resets the flat-gradient bookkeeping
@@ -212,6 +254,7 @@ class FusedAdamClip(torch.optim.Optimizer):
                                    "re-homed by a DDP wrapper): reduce model._flat_grad itself, or step with torch.optim.Adam")
         pg = self.param_groups[0]
         self.step_count += 1
+        self._staging = None          # (gather_state: the moments are about to change)
         if hasattr(self.model, "_drop_eval_g"):
             self.model._drop_eval_g()          # the kernel writes the parameters through raw pointers (no version bump): STEP's kept eval-mode g is stale
         extra = None
@@ -246,17 +289,64 @@ class FusedAdamClip(torch.optim.Optimizer):
         While a ``GraphedTrainStep`` is attached the step count is on the device: ``close()`` it first.
         With a sharded graph learner (``discrete_graph_learning._shard``) the flat buffer holds this rank's ``fc.weight`` slice, which
         is no parameter of torch's format: there both methods keep the flat per-rank format ``{"step", "exp_avg", "exp_avg_sq",
-        "param_groups"}`` (one file per rank)."""
+        "param_groups"}`` (one file per rank) -- unless the optimizer was built with ``gathered_state=True``: then it is torch's format
+        here too, ``fc.weight``'s entry holding the full moments that ``gather_state()`` assembled on the group's rank 0.  Once a step
+        has run, a ``state_dict()`` without a gather since the last step -- or on another rank than the one that holds the gathered
+        moments -- raises ``RuntimeError``: one rank's slice is never written as if it were the whole."""
         if self._index is None:
             groups = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
             return {"step": self.step_count, "exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "param_groups": groups}
-        return {"state": moments_to_state(self._index, self.exp_avg, self.exp_avg_sq, self.step_count),
+        gathered = None
+        if self._sliced is not None and self.step_count > 0:
+            gathered = self._staging
+            if gathered is None:
+                raise RuntimeError("FusedAdamClip: the graph learner is sharded in time slices and this optimizer has stepped since the "
+                                   "last gather: call gather_state() on ALL ranks (e.g. in the runner's on_epoch_end) before "
+                                   "state_dict() -- the flat buffers hold the moments of this rank's fc.weight slice only")
+            if sorted(gathered) != sorted(self._sliced):
+                raise RuntimeError("FusedAdamClip: gather_state() assembled fc.weight's moments on the group's rank 0; this rank holds "
+                                   "its slice only and has no complete state_dict() to give")
+        return {"state": moments_to_state(self._index, self.exp_avg, self.exp_avg_sq, self.step_count, gathered),
                 "param_groups": [adam_group(self.param_groups[0], len(self._label))]}
+
+    def gather_state(self, process_group=None):
+        """Collective (``gathered_state=True`` with a sharded graph learner; a no-op otherwise): assemble the full ``exp_avg`` /
+        ``exp_avg_sq`` of ``fc.weight`` on the group's rank 0, in two staging tensors of ``fc.weight``'s shape, for ``state_dict()``.
+        One broadcast per rank and moment, each of that rank's slice straight out of its flat buffer; a rank that is neither the
+        sender nor rank 0 receives into a temporary of one slice.  The staging stays valid until the next ``step()``,
+        ``load_state_dict()`` or ``release_state()``."""
+        if self._sliced is None:
+            return
+        import torch.distributed as dist
+        dgl = self.model.discrete_graph_learning
+        sh = dgl._shard
+        (at, (T2, _, _)), = self._sliced.items()
+        _, off, p = self._index[at]
+        root = sh["rank"] == 0
+        staged = tuple(torch.empty(p.shape, dtype=buf.dtype, device=buf.device) for buf in (self.exp_avg, self.exp_avg_sq)) if root else ()
+        for r in range(sh["world"]):
+            a, b = sh["bounds"][r], sh["bounds"][r + 1]
+            n = p.shape[0] * (p.shape[1] // T2) * (b - a)
+            src = dist.get_global_rank(process_group, r) if process_group is not None else r
+            for k, buf in enumerate((self.exp_avg, self.exp_avg_sq)):
+                piece = buf[off:off + n] if r == sh["rank"] else torch.empty(n, dtype=buf.dtype, device=buf.device)
+                if sh["world"] > 1:
+                    dist.broadcast(piece, src, group=process_group)
+                if root:
+                    paste_time_columns(staged[k], T2, a, b, piece)
+                del piece
+        self._staging = {at: staged} if root else {}
+
+    def release_state(self):
+        """drop what ``gather_state()`` assembled (two tensors of ``fc.weight``'s size on rank 0)"""
+        self._staging = None
 
     def load_state_dict(self, sd):
         """torch's format (see ``state_dict``; ``ValueError`` for a state the fused pass cannot hold: another shape, an entry for a
         parameter outside the flat buffer, entries for only some parameters, different step counts), or the flat format of
-        checkpoints written before (``"exp_avg"`` as a top-level key)"""
+        checkpoints written before (``"exp_avg"`` as a top-level key).  With ``gathered_state=True`` over a sharded graph learner:
+        torch's format with ``fc.weight``'s moments in the full shape, of which this rank keeps its columns -- no collective, every
+        rank reads the same state."""
         if "exp_avg" in sd:
             self.step_count = _step_value(sd["step"])
             self.exp_avg.copy_(sd["exp_avg"])
@@ -264,6 +354,7 @@ class FusedAdamClip(torch.optim.Optimizer):
         elif self._index is None:
             raise ValueError("FusedAdamClip: with a sharded graph learner the optimizer state is the flat per-rank format, not torch's")
         else:
-            self.step_count = state_to_moments(self._index, self._label, sd, self.exp_avg, self.exp_avg_sq)
+            self.step_count = state_to_moments(self._index, self._label, sd, self.exp_avg, self.exp_avg_sq, self._sliced)
+        self._staging = None          # (after the copies: the loaded entries may be the staging's own tensors)
         for g, src in zip(self.param_groups, sd["param_groups"]):
             g.update({k: v for k, v in src.items() if k != "params"})

@@ -43,6 +43,8 @@ A launch on several GPUs (``CFG.GPU_NUM = 2``, the reference's default) hands th
 the reducer owns the gradients and all of the above but the loaders is off.  ``native_runner(..., native_data_parallel=True)`` takes the
 module out of the wrap in ``init_training`` and calls its ``enable_native_data_parallel()`` (the flat gradient buffer averaged inside
 backward), and checks once per epoch that the ranks' parameters are still the same bits (``step_amd.comm.replicas_identical``).
+``shard_graph_learner=True`` on top of it cuts STEP's graph learner in time slices over the ranks and gathers them at the end of every
+epoch, so that rank 0 validates the whole learner and writes one checkpoint in the reference's format.
 
 Nothing here imports the reference or easytorch: the base class is handed in by the config file, which lives in the reference tree.
 """
@@ -320,6 +322,22 @@ def hand_over_training_state(old_optim, old_scheduler, new_optim, scheduler_para
     return new
 
 
+MIN_SLICE_COLUMNS = 128          # the sliced backward's floor (step_dgl_global_backward_shard): conv2-output columns per rank
+
+
+def shard_decision(matmul_precision, T2, world, optimizer_swappable):
+    """One rank's vote on ``shard_graph_learner`` -- the ranks take the MIN of their votes before anyone slices.  True when the graph
+    learner's global branch can be cut in time slices here: the bf16 contraction mode (the sliced backward has no f32 form), every
+    slice of ``DiscreteGraphLearning.slice_bounds(T2, world)`` at least ``MIN_SLICE_COLUMNS`` wide (``T2 = train_length - 18``
+    conv2-output columns), and the fused optimizer about to be swapped in (the slice's gradient lives in the flat buffer only).
+    Anything else: data-parallel with the whole learner on every rank."""
+    from .step_arch.discrete_graph_learning import DiscreteGraphLearning
+    if matmul_precision != "bf16" or not optimizer_swappable or int(world) < 2:
+        return False
+    bounds = DiscreteGraphLearning.slice_bounds(int(T2), int(world))
+    return min(bounds[r + 1] - bounds[r] for r in range(int(world))) >= MIN_SLICE_COLUMNS
+
+
 class _Deferred:
     """what a metric returns while the meters are deferred: ``.item()`` hands back the device value instead of waiting for it"""
 
@@ -332,7 +350,7 @@ class _Deferred:
 
 def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, encoder_workgroups=None, native_metrics=True,
                   eval_cache_bytes=0, native_tail=False, native_pretrain=False, native_data_parallel=False, replica_check=True,
-                  native_eval=False, eval_batch_size=None, accumulate=1):
+                  native_eval=False, eval_batch_size=None, accumulate=1, shard_graph_learner=False):
     """-> subclass of ``base`` (the reference's ``STEPRunner``, or any ``BaseTimeSeriesForecastingRunner``) for ``CFG.RUNNER``.
     ``encoder_workgroups``: compute units of the persistent encoder launch next to the step (None: 160 at 307 nodes / 336 tokens, the
     measured optimum of config C2; 0: one workgroup per sequence) -- only used while batches are prefetched.
@@ -358,9 +376,20 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
     that everything above acts as for one process: the fused optimizer, the native tail, ``native_pretrain``.  It acts only when
     ``torch.distributed`` is initialised with more than one rank and EVERY rank holds a ``STEP``, or a ``TSFormer`` in pre-train mode,
     on a GPU (one MIN all-reduce; otherwise nothing is unwrapped anywhere and rank 0 warns).  Checkpoints keep the reference's keys
-    either way.  The graph learner's time slices (``shard_graph_learner``) are not used under the runner.
+    either way.
+    ``shard_graph_learner``: where ``native_data_parallel`` acts on a ``STEP`` (a pre-training ``TSFormer`` has no graph learner:
+    nothing changes there), every rank keeps one time slice of the graph learner's global branch and the matching columns of
+    ``fc.weight`` (``STEP.enable_native_data_parallel(shard_graph_learner=True)``): the 87 MB ``fc.weight`` gradient of STEP_PEMS04
+    never enters a collective.  The ranks vote in the same MIN all-reduce (``shard_decision``: bf16 mode, slices of at least 128
+    columns, the fused optimizer swappable); if any rank cannot, rank 0 warns and every rank trains with the whole learner.  The
+    fused optimizer is built with ``gathered_state=True``, so resumed torch-format moments are cut to the rank's columns.  At the
+    end of every epoch ALL ranks gather -- ``fc.weight``, then its two moments onto rank 0 -- before the base class's
+    ``on_epoch_end`` (or, for a base without one, before ``save_model``): rank 0's validation and test run the whole learner
+    without a collective, and its checkpoint has the reference's keys and torch Adam's format, so it resumes sliced, unsliced, in
+    one process or under the reference's runner.  Not together with ``accumulate > 1`` (``init_training`` raises ``ValueError``).
     ``replica_check``: with ``native_data_parallel`` acting, the first iteration of every epoch starts by comparing a 128-bit digest of
-    the ranks' flat parameter buffers (``step_amd.comm.replicas_identical``: one kernel, one 32-byte collective, one read-back); every
+    the ranks' flat parameter buffers (``step_amd.comm.replicas_identical``: one kernel, one 32-byte collective, one read-back; with
+    ``shard_graph_learner`` acting, of the replicated part in front of the ``fc.weight`` slice, which has no replica); every
     rank raises ``RuntimeError`` when they differ -- only rank 0 writes the checkpoint, and no wrapper guarantees identical replicas.
     The buffer is the one the fused optimizer updates: where ``init_training`` keeps torch's optimizer there is none and nothing is
     checked.
@@ -402,6 +431,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             self._pending = {}          # meter name -> [(device value, n), ...] since the last flush
             self._metric_cache = None
             self._dp_acting = False          # native_data_parallel took the module out of its DistributedDataParallel wrap
+            self._shard_acting = False          # ... and shard_graph_learner cut the graph learner in time slices
             self._val_metrics = None          # native_eval: (what it was built for, the validation pass's EvalMetrics)
             self._group_size, self._group_pos = 1, 0          # accumulate: size of the open group, iterations of it that ran backward
 
@@ -495,9 +525,17 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                     and next(model.parameters()).is_cuda)
             # a mixed decision would deadlock the first collective: one MIN all-reduce before anyone acts
             dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
-            every = torch.tensor([1 if able else 0], dtype=torch.int32, device=dev)
+            votes = [1 if able else 0]
+            if shard_graph_learner:
+                # the same collective carries the vote on the time slices: no rank may reach shard_time_slices alone
+                slices = able and isinstance(model, STEP) and shard_decision(
+                    model.matmul_precision, model.discrete_graph_learning.train_length - 18, dist.get_world_size(),
+                    self._fused_swap_ok(model, getattr(self, "optim", None), False))
+                votes.append(1 if slices else 0)
+            every = torch.tensor(votes, dtype=torch.int32, device=dev)
             dist.all_reduce(every, op=dist.ReduceOp.MIN)
-            if int(every.item()) == 0:
+            every = every.tolist()
+            if every[0] == 0:
                 if dist.get_rank() == 0:
                     import warnings
                     warnings.warn("step_amd.runner: native_data_parallel needs a STEP, or a TSFormer in pre-train mode, on a GPU on every "
@@ -509,10 +547,26 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                 self.model = model
                 import gc
                 gc.collect()
+            if shard_graph_learner and isinstance(model, STEP) and every[1] == 0:
+                if dist.get_rank() == 0:
+                    import warnings
+                    warnings.warn("step_amd.runner: shard_graph_learner needs, on every rank, matmul_precision = 'bf16', time slices of "
+                                  f"at least {MIN_SLICE_COLUMNS} columns and the fused optimizer (fused_optimizer=True around a plain "
+                                  "torch.optim.Adam with one parameter group and a 2-norm clip); every rank trains data-parallel with "
+                                  "the whole graph learner")
+            if shard_graph_learner and every[1] == 1:
+                # (after the resume: the slice is cut from the resumed, broadcast fc.weight)
+                model.enable_native_data_parallel(collectives="auto", sync_module_states=True, shard_graph_learner=True)
+                self._shard_acting = True
+                return True
             model.enable_native_data_parallel(collectives="auto", sync_module_states=True)          # (after the resume: resumed weights are broadcast)
             return True
 
         def init_training(self, cfg):
+            if native_data_parallel and shard_graph_learner and accumulate > 1:
+                # the module refuses a group of backwards over time slices; said here, by the options' names, on every rank alike
+                raise ValueError(f"step_amd.runner: shard_graph_learner=True cannot be combined with accumulate={accumulate}: a time-sliced "
+                                 "graph learner takes one backward per optimizer step (set accumulate=1, or shard_graph_learner=False)")
             super().init_training(cfg)
             self._dp_acting = self._enable_data_parallel() if native_data_parallel else False
             model = _unwrap(self.model)
@@ -526,23 +580,34 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                                    "any wrapper, and a plain torch.optim.Adam with one parameter group and a 2-norm clip): training on "
                                    "with another effective batch size would be silent")
 
-        def _swap_optimizer(self, cfg, model, opt, pretrain):
-            if not (fused_optimizer and (isinstance(model, STEP) or pretrain) and model is self.model and type(opt) is torch.optim.Adam
+        def _fused_swap_ok(self, model, opt, pretrain):
+            """what ``_swap_optimizer`` asks of the bare module, the optimizer and the clip (the vote on the time slices asks the same
+            while the module is still wrapped)"""
+            if not (fused_optimizer and (isinstance(model, STEP) or pretrain) and type(opt) is torch.optim.Adam
                     and next(model.parameters()).is_cuda):
-                return          # (under a DistributedDataParallel wrap the reducer owns the .grad tensors: torch's optimizer stays)
-            from .optim import FusedAdamClip
+                return False
             g = opt.param_groups[0]
             if len(opt.param_groups) != 1 or g.get("amsgrad") or g.get("maximize"):
-                return
+                return False
             clip = getattr(self, "clip_grad_param", None) or {}
-            if clip and float(clip.get("norm_type", 2.0)) != 2.0:
+            return not (clip and float(clip.get("norm_type", 2.0)) != 2.0)
+
+        def _swap_optimizer(self, cfg, model, opt, pretrain):
+            # (under a DistributedDataParallel wrap the reducer owns the .grad tensors: torch's optimizer stays)
+            if not (model is self.model and self._fused_swap_ok(model, opt, pretrain)):
+                if self._shard_acting:
+                    raise RuntimeError("step_amd.runner: the graph learner is in time slices but the fused optimizer was not swapped in")
                 return
+            from .optim import FusedAdamClip
+            g = opt.param_groups[0]
+            clip = getattr(self, "clip_grad_param", None) or {}
             if pretrain:
                 model.flatten_parameters()          # (values and state_dict unchanged: every parameter becomes a view into one buffer)
             # positions in the replaced Adam's own list are the indices of the optimizer state on disk, whether easytorch handed it
             # model.parameters() or only the trainable ones
             fused = FusedAdamClip(model, lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"],
-                                  max_norm=clip.get("max_norm"), param_grads=pretrain, params=g["params"])
+                                  max_norm=clip.get("max_norm"), param_grads=pretrain, params=g["params"],
+                                  gathered_state=self._shard_acting)
             sched = getattr(self, "scheduler", None)
             s = cfg["TRAIN"].get("LR_SCHEDULER") if sched is not None else None
             self.scheduler = hand_over_training_state(opt, sched, fused, s["PARAM"] if s is not None else None)
@@ -576,10 +641,15 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
         def _check_replicas(self, epoch):
             """every rank runs train_iters (validation and its hooks run on rank 0 only): all ranks see the same answer and raise together.
             Without a flat parameter buffer (the fused optimizer was not swapped in: the same config decision on every rank) there is
-            nothing to digest and nothing is checked"""
+            nothing to digest and nothing is checked.  With the graph learner in time slices the buffer ends in this rank's ``fc.weight``
+            slice, which differs between the ranks by design and has no replica to be compared against: only the replicated prefix --
+            everything in front of the layout's ``norm_slot``, the same length on every rank -- is digested"""
             import torch.distributed as dist
             from .comm import replicas_identical
-            flat = _unwrap(self.model)._flat_param
+            model = _unwrap(self.model)
+            flat = model._flat_param
+            if flat is not None and self._shard_acting:
+                flat = flat[:model._grad_layout()["norm_slot"]]
             if flat is not None and not replicas_identical(flat):
                 raise RuntimeError(f"step_amd.runner: the data-parallel replicas differ at the start of epoch {epoch} (rank "
                                    f"{dist.get_rank()} of {dist.get_world_size()}): the ranks' flat parameter buffers do not hold the same "
@@ -835,6 +905,34 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
         def on_validating_end(self, *args, **kwargs):
             self.flush_meters()          # (base_tsf_runner.py:321-329 picks the best model by the epoch's val_MAE)
             return super().on_validating_end(*args, **kwargs)
+
+        # ---------------------------------------------------------------- the epoch's end with the graph learner in time slices
+        def _gather_slices(self):
+            """ALL ranks: every rank's ``fc.weight`` slice into every rank's ``fc.weight`` (one gather of the matrix), then the two
+            moments of the slices onto rank 0 (two more).  What follows on rank 0 alone -- the master-only validation, test and
+            ``save_model`` -- then runs the whole graph learner without a collective and writes a complete checkpoint"""
+            model = _unwrap(self.model)
+            model.discrete_graph_learning.gather_fc_weight(model._process_group)
+            self.optim.gather_state(model._process_group)
+
+        def _with_gathered_slices(self, then, *args, **kwargs):
+            if not self._shard_acting:
+                return then(*args, **kwargs)
+            self._gather_slices()
+            try:
+                return then(*args, **kwargs)
+            finally:
+                self.optim.release_state()
+
+        if hasattr(base, "on_epoch_end"):
+            def on_epoch_end(self, *args, **kwargs):
+                """``basicts/runners/base_runner.py:132-152`` runs on every rank and calls the master-only ``validate``, ``test_process``
+                and ``save_model``: the slices are gathered in front of it, the staging is released behind it"""
+                return self._with_gathered_slices(super().on_epoch_end, *args, **kwargs)
+        elif hasattr(base, "save_model"):
+            def save_model(self, *args, **kwargs):
+                """a base without ``on_epoch_end``: the same in front of ``save_model``, which every rank has to call"""
+                return self._with_gathered_slices(super().save_model, *args, **kwargs)
 
     NativeRunner.__name__ = "Native" + base.__name__
     NativeRunner.__qualname__ = NativeRunner.__name__

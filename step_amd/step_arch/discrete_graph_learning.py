@@ -36,6 +36,20 @@ def _load_pkl(path):
             return pickle.load(f, encoding="latin1")
 
 
+def cut_time_columns(full, T2, a, b):
+    """columns [a, b) of the ``[rows, channels, T2]`` view of a ``[rows, channels*T2]`` matrix (``fc.weight``, or a moment of it) as a
+    new contiguous ``[rows, channels*(b-a)]`` matrix: a time slice's share, in the layout of ``fc_weight_slice``"""
+    rows = full.shape[0]
+    return full.view(rows, -1, T2)[:, :, a:b].contiguous().view(rows, -1)
+
+
+def paste_time_columns(full, T2, a, b, piece):
+    """the inverse of ``cut_time_columns``, in place: ``piece`` (``b - a`` columns per channel, any shape of that many values per
+    row) becomes columns [a, b) of ``full``'s ``[rows, channels, T2]`` view"""
+    rows = full.shape[0]
+    full.view(rows, -1, T2)[:, :, a:b].copy_(piece.view(rows, -1, b - a))
+
+
 class DiscreteGraphLearning(nn.Module):
     def __init__(self, dataset_name, k, input_seq_len, output_seq_len, num_nodes=None, train_length=None, data=None,
                  tsformer_tokens=None):
@@ -96,8 +110,7 @@ class DiscreteGraphLearning(nn.Module):
                        "own1": (b - a) + (9 if rank == world - 1 else 0),
                        "count1": float(self.num_nodes) * (self.train_length - 9), "count2": float(self.num_nodes) * T2}
         self.register_buffer("_series_slice", self._series_nt[:, a:b + 18].contiguous(), persistent=False)
-        w = self.fc.weight.detach().view(self.embedding_dim, 16, T2)[:, :, a:b].contiguous().view(self.embedding_dim, -1)
-        self.fc_weight_slice = nn.Parameter(w.clone())
+        self.fc_weight_slice = nn.Parameter(cut_time_columns(self.fc.weight.detach(), T2, a, b).clone())
         self.fc.weight.requires_grad_(False)
         self._slice_dirty = False            # set by the native backward: fc.weight no longer holds what the slices hold
         return self._shard
@@ -116,13 +129,13 @@ class DiscreteGraphLearning(nn.Module):
         if sh is None:
             return
         T2 = self.train_length - 18
-        full = self.fc.weight.data.view(self.embedding_dim, 16, T2)
+        full = self.fc.weight.data
         for r in range(sh["world"]):
             a, b = sh["bounds"][r], sh["bounds"][r + 1]
             buf = self.fc_weight_slice.data.view(self.embedding_dim, 16, b - a).clone() if r == sh["rank"] else \
                 torch.empty(self.embedding_dim, 16, b - a, device=full.device, dtype=full.dtype)
             dist.broadcast(buf, dist.get_global_rank(process_group, r) if process_group is not None else r, group=process_group)
-            full[:, :, a:b].copy_(buf)
+            paste_time_columns(full, T2, a, b, buf)
         self._slice_dirty = False
         self._gather_count = getattr(self, "_gather_count", 0) + 1      # fc.weight.data was written in place (no version bump): STEP's kept eval-mode g is stale
 
@@ -132,7 +145,7 @@ class DiscreteGraphLearning(nn.Module):
         if sh is not None:
             T2 = self.train_length - 18
             with torch.no_grad():
-                self.fc_weight_slice.copy_(self.fc.weight.view(self.embedding_dim, 16, T2)[:, :, sh["a"]:sh["b"]].reshape(self.embedding_dim, -1))
+                self.fc_weight_slice.copy_(cut_time_columns(self.fc.weight, T2, sh["a"], sh["b"]))
 
     def state_dict(self, *args, **kwargs):
         if self._shard is not None and self._slice_dirty:
