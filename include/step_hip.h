@@ -216,6 +216,16 @@ long step_dgl_edges_work_floats(int N);
 long step_dgl_edges_theta_offset(int N);      /* theta_out == saved + this offset (floats): theta is written once, in place (no copy) */
 int step_dgl_edges_forward(const float* g, int N, int B, const StepDglParams* p, const float* u, uint64_t seed,
                            float temperature, float* saved, float* theta_out, float* adj_out, void* stream);
+/* The same forward with the Gumbel noise keyed by the sample instead of by its position in the batch (additive to ABI 10).  The graph
+ * learner samples in eval mode too (discrete_graph_learning.py:170-171); with the positional stream a window's graph depends on where in
+ * which batch it sits.  Here sample b, edge e = i * N + j draw
+ *     philox4x32(c0 = e, c1 = low 32 bits of key[b], c2 = high 32 bits of key[b], c3 = 0x5EEE, k0 / k1 = low / high 32 bits of seed),
+ * u0 / u1 = words 0 / 1 through (x >> 8) * 2^-24; everything after u0, u1 is the same kernel.  The tag 0x5EEE keeps the stream disjoint
+ * from the positional one (c = (e_lo, e_hi, b, 0x5EED)) under one seed.
+ *  key   int64 [B] on the device, read there (a forecast origin: the module passes the window indices it already holds on the device)
+ * saved / theta_out / adj_out: layout and meaning as above, diagonal cleared.  N > 65535 (an e that does not fit c0) -> STEP_ERR_ARG. */
+int step_dgl_edges_forward_keyed(const float* g, int N, int B, const StepDglParams* p, const long* key, uint64_t seed,
+                                 float temperature, float* saved, float* theta_out, float* adj_out, void* stream);
 /* aux_stream (nullable): the fc_out weight / bias gradients are queued there, ordered after the kernels that produce their inputs and
  * NOT joined (same contract as step_gwnet_backward: order the first reader of `grads` and the release of `work` after aux_stream);
  * dg is ordered on `stream`. */

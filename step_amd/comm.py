@@ -90,6 +90,27 @@ def broadcast_module_states(module, process_group):
                 d.copy_(c)
 
 
+def broadcast_running_statistics(module, process_group):
+    """Every rank takes rank 0's BatchNorm running statistics, in ONE broadcast of their concatenation.  Native data parallel keeps the
+    parameters identical, but each rank's BatchNorm layers see that rank's batches, so the running statistics drift apart;
+    ``DistributedDataParallel`` hands rank 0's buffers to every rank before each forward (``broadcast_buffers``), which is why rank 0's
+    master-only evaluation and its checkpoint are THE run's.  A rank that evaluates a share of a pass needs the same statistics.  Training
+    does not read them (train mode normalises with the batch's), so the parameters' trajectory is untouched.  -> floats sent"""
+    import torch.distributed as dist
+    bufs = [b for name, b in module.named_buffers() if name.endswith(("running_mean", "running_var")) and b.dtype == torch.float32]
+    if not bufs:
+        return 0
+    with torch.no_grad():
+        flat = torch.cat([b.detach().reshape(-1) for b in bufs])
+        dist.broadcast(flat, dist.get_global_rank(process_group, 0) if process_group is not None else 0, group=process_group)
+        if dist.get_rank(process_group) != 0:
+            at = 0
+            for b in bufs:
+                b.copy_(flat[at:at + b.numel()].view_as(b))
+                at += b.numel()
+    return int(flat.numel())
+
+
 def replica_digest(flat):
     """-> int64 ``[2]`` on ``flat``'s device: the two 64-bit words of ``step_replica_digest`` (the sum mod 2^64 and the xor of one
     splitmix64-mixed word per element and position; uint64 bit patterns, exposed as int64 since torch has no uint64 arithmetic).

@@ -469,17 +469,27 @@ __global__ __launch_bounds__(256) void edge_logit_kernel(const float* __restrict
 }
 
 // theta[b][e] = sigmoid(z[e]);  y0 = sigmoid((z + g0 - g1)/tau), adj = [y0 >= y1] with the diagonal cleared
+// KEYED: the noise of sample b is a function of (edge, key[b], seed) instead of (edge, b, seed) -- a window draws the same graph wherever
+// it sits in whichever batch (step_dgl_edges_forward_keyed; u and dyn are NULL, N <= 65535 so that e fits one counter word).  The key is
+// uniform over the workgroup (b = blockIdx.y): one 8-byte load.  The tag 0x5EEE keeps the stream apart from the positional 0x5EED.
+template <bool KEYED>
 __global__ __launch_bounds__(256) void gumbel_sample_kernel(const float* __restrict__ z, const float* __restrict__ u, int B, int N,
                                                             uint32_t seed_lo, uint32_t seed_hi, float inv_tau,
                                                             float* __restrict__ theta, float* __restrict__ y0, float* __restrict__ adj,
-                                                            const StepDynState* __restrict__ dyn) {
+                                                            const StepDynState* __restrict__ dyn, const long* __restrict__ key) {
     if (dyn) { const uint64_t x = dyn->seed_xor; seed_lo ^= (uint32_t)x; seed_hi ^= (uint32_t)(x >> 32); }      // replayed steps (step_hip.h)
     const long E = (long)N * N;
     const int b = blockIdx.y;
+    uint32_t key_lo = 0, key_hi = 0;
+    if (KEYED) { const uint64_t k = (uint64_t)key[b]; key_lo = (uint32_t)k; key_hi = (uint32_t)(k >> 32); }
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < E; e += (long)gridDim.x * 256) {
         const float zv = z[e];
         float u0, u1;
-        if (u) {
+        if (KEYED) {
+            uint32_t r[4];
+            philox4x32((uint32_t)e, key_lo, key_hi, 0x5EEEu, seed_lo, seed_hi, r);
+            u0 = u32_to_unit(r[0]); u1 = u32_to_unit(r[1]);
+        } else if (u) {
             u0 = u[((long)b * E + e) * 2];
             u1 = u[((long)b * E + e) * 2 + 1];
         } else {
@@ -1124,10 +1134,24 @@ extern "C" int step_dgl_edges_forward(const float* g, int N, int B, const StepDg
                                       float temperature, float* saved, float* theta_out, float* adj_out, void* stream) {
     return step_dgl_edges_forward_dyn(g, N, B, p, u, seed, temperature, saved, theta_out, adj_out, nullptr, stream);
 }
+static int dgl_edges_forward_impl(const float* g, int N, int B, const StepDglParams* p, const float* u, const long* key, uint64_t seed,
+                                  float temperature, float* saved, float* theta_out, float* adj_out, const StepDynState* dyn, void* stream);
 extern "C" int step_dgl_edges_forward_dyn(const float* g, int N, int B, const StepDglParams* p, const float* u, uint64_t seed,
                                           float temperature, float* saved, float* theta_out, float* adj_out, const StepDynState* dyn,
                                           void* stream) {
     STEP_REQUIRE(g && p && saved && adj_out && N > 0 && B > 0 && temperature > 0.f, "dgl_edges_forward: bad arguments");
+    return dgl_edges_forward_impl(g, N, B, p, u, nullptr, seed, temperature, saved, theta_out, adj_out, dyn, stream);
+}
+// The same with the Gumbel noise keyed by a per-sample int64 read on the device: sample b, edge e = i*N + j draw
+// philox4x32(e, lo32(key[b]), hi32(key[b]), 0x5EEE; seed) -- words 0 and 1 through u32_to_unit -- and everything after is the kernel above.
+extern "C" int step_dgl_edges_forward_keyed(const float* g, int N, int B, const StepDglParams* p, const long* key, uint64_t seed,
+                                            float temperature, float* saved, float* theta_out, float* adj_out, void* stream) {
+    STEP_REQUIRE(g && p && key && saved && adj_out && N > 0 && B > 0 && temperature > 0.f, "dgl_edges_forward_keyed: bad arguments");
+    STEP_REQUIRE(N <= 65535, "dgl_edges_forward_keyed: N > 65535 (the edge index must fit one 32-bit counter word)");
+    return dgl_edges_forward_impl(g, N, B, p, nullptr, key, seed, temperature, saved, theta_out, adj_out, nullptr, stream);
+}
+static int dgl_edges_forward_impl(const float* g, int N, int B, const StepDglParams* p, const float* u, const long* key, uint64_t seed,
+                                  float temperature, float* saved, float* theta_out, float* adj_out, const StepDynState* dyn, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     float* sndT = saved;
     float* rcv = sndT + (long)N * EMB;
@@ -1149,7 +1173,10 @@ extern "C" int step_dgl_edges_forward_dyn(const float* g, int N, int B, const St
     STEP_LAUNCH_CHECK("edge_logit");
     int gx = cdiv((long)N * N, 256);
     if (gx > 4096) gx = 4096;
-    gumbel_sample_kernel<<<dim3(gx, B), 256, 0, st>>>(z, u, B, N, (uint32_t)seed, (uint32_t)(seed >> 32), 1.f / temperature, theta, y0, adj_out, dyn);
+    if (key)
+        gumbel_sample_kernel<true><<<dim3(gx, B), 256, 0, st>>>(z, nullptr, B, N, (uint32_t)seed, (uint32_t)(seed >> 32), 1.f / temperature, theta, y0, adj_out, nullptr, key);
+    else
+        gumbel_sample_kernel<false><<<dim3(gx, B), 256, 0, st>>>(z, u, B, N, (uint32_t)seed, (uint32_t)(seed >> 32), 1.f / temperature, theta, y0, adj_out, dyn, nullptr);
     STEP_LAUNCH_CHECK("gumbel_sample");
     if (theta_out && theta_out != theta) {
         if (hipMemcpyAsync(theta_out, theta, (size_t)B * N * N * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {

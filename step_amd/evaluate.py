@@ -12,7 +12,9 @@ three numbers back per batch.  ``EvalMetrics`` gives both tables from one launch
 
 ``STEP.evaluate(loader, origins, ...)`` (``evaluate_pass`` below) is that loop over a device-resident series.  In eval mode every window
 is independent of its batch (BatchNorm uses its running statistics, nothing needs a gradient), so ``batch_size`` may be much larger than
-the training configuration's: the host work of a forward is then shared by more windows.
+the training configuration's: the host work of a forward is then shared by more windows.  The one thing that ties a window to its batch
+is the graph learner's eval-mode sampling under ``STEP.eval_noise = "position"``; with ``"window"`` a pass is a function of the weights
+and the windows alone, and ``evaluate_pass(..., process_group=)`` / ``EvalMetrics.all_reduce`` spread it over ranks.
 """
 import ctypes
 import math
@@ -76,10 +78,12 @@ class EvalMetrics:
         self._acc = torch.zeros(n, dtype=torch.float64, device=dev)
         self._out = torch.empty((self.horizons + 2) * 3, dtype=torch.float64, device=dev)
         self.batches = 0
+        self._reduced = False          # all_reduce ran since the last reset: the count of updates is the device's
 
     def reset(self):
         self._acc.zero_()
         self.batches = 0
+        self._reduced = False
 
     def update(self, pred, real, group=None):
         """one accumulate launch over the whole of ``pred`` / ``real``; with ``group = g`` one launch per ``g`` consecutive windows
@@ -113,9 +117,30 @@ class EvalMetrics:
         if any(not 0 <= h < H for h in rows):
             raise ValueError(f"EvalMetrics.result: horizons {rows} not all in 0..{H - 1}")
         _lib.call("step_eval_metrics_finish", _lib.ptr(self._acc), H, _lib.ptr(self._out), _lib.stream())
-        table = self._out.cpu().numpy().reshape(H + 2, 3)
+        # after all_reduce the accumulator's count of updates (slot 5H + 8, summed over the ranks) comes back with the table, in the one copy
+        out = torch.cat([self._out, self._acc[5 * H + 8:5 * H + 9]]) if self._reduced else self._out
+        flat = out.cpu().numpy()
+        if self._reduced:
+            self.batches = int(round(flat[-1]))
+        table = flat[:(H + 2) * 3].reshape(H + 2, 3)
         return EvalResult(per_horizon=table[list(rows)].copy(), overall=table[H].copy(), batch_mean=table[H + 1].copy(),
                           batches=self.batches, horizons=rows)
+
+    def all_reduce(self, process_group=None):
+        """Merge the accumulators of the ranks of ``process_group`` (None: the default group): ONE SUM all-reduce of the f64
+        accumulator through ``torch.distributed``, in place on the device, nothing read back.  Every rank calls it once, between its
+        last ``update`` and ``result``; afterwards every rank holds the pass of all ranks' updates together, and ``batches`` is the sum
+        over the ranks from the next ``result()`` on (it is the accumulator's own count of updates and comes back with the table).
+
+        Why a plain sum is the merge (accumulator layout of ``csrc/eval_metrics.hip``, H horizons): slots ``[0, 5H)`` are the five sums
+        (|err|, err^2, count, APE, its count) per horizon over all updates, ``[5H+5, 5H+8)`` the sum over updates of each update's own
+        MAE / RMSE / MAPE and ``5H+8`` the number of updates -- all sums of per-update terms, so the sum over ranks is what one
+        accumulator fed every update would hold, up to the order of the f64 additions.  The per-call slots ``[5H, 5H+5)`` and the ticket
+        ``5H+9`` are zero between calls on every rank, and 0 + 0 = 0 keeps them so.  ``result`` then divides as always.  A rank
+        without any update contributes zeros."""
+        import torch.distributed as dist
+        dist.all_reduce(self._acc, op=dist.ReduceOp.SUM, group=process_group)
+        self._reduced = True
 
 
 def _scale_shift(scaler):
@@ -134,15 +159,38 @@ def _scale_shift(scaler):
     return std, mean
 
 
+def eval_rank_chunks(n_chunks, rank, world):
+    """The chunks (batches) of an evaluation pass that ``rank`` of ``world`` evaluates when the pass is spread over the ranks: chunk
+    ``c`` belongs to rank ``c % world``.  Every chunk keeps the composition it has in a single-process pass; only who runs it changes."""
+    n_chunks, rank, world = int(n_chunks), int(rank), int(world)
+    if world < 1 or not 0 <= rank < world or n_chunks < 0:
+        raise ValueError(f"eval_rank_chunks: n_chunks = {n_chunks}, rank = {rank}, world = {world}")
+    return list(range(rank, n_chunks, world))
+
+
 def evaluate_pass(model, loader, origins=None, scaler=None, null_val=0.0, batch_size=None, target_channel=0, horizons=None,
-                  return_predictions=False):
+                  return_predictions=False, process_group=None):
     """``STEP.evaluate``: one validation / test pass of ``model`` over the windows at ``origins`` (host integers, walked in order in chunks
     of ``batch_size``, default 8).  ``loader``: a ``DeviceWindowLoader``, or a ``DeviceForecastingDataset`` (``origins`` then defaults to
     its index).  Every chunk is one forward in eval mode under ``torch.no_grad()`` followed by one ``EvalMetrics.update`` against channel
     ``target_channel`` of the future window; nothing is read back before the table.  ``scaler``: see ``_scale_shift``.  ``horizons``: the rows
     reported (the reference's ``EVALUATION_HORIZONS``; default all).  Returns an ``EvalResult``, with ``return_predictions=True`` the
-    pair ``(EvalResult, normalised predictions [W, H, N] on the device)``.  The ``training`` flag is restored on exit."""
+    pair ``(EvalResult, normalised predictions [W, H, N] on the device)``.  The ``training`` flag is restored on exit.
+
+    ``process_group`` (a ``torch.distributed`` group every rank of which makes this call with the same arguments): the pass is spread
+    over its ranks -- chunk ``c`` is evaluated by rank ``c % world`` (``eval_rank_chunks``) with the composition it has in a
+    single-process pass, all ranks draw the graph learner's noise under rank 0's eval seed (one small broadcast), the tables are merged by
+    ``EvalMetrics.all_reduce`` and every rank returns the whole pass.  That needs a pass that does not depend on who evaluates what:
+    ``model.eval_noise == "window"``; and ``return_predictions=False`` (no rank holds them all).  Either violation raises ``ValueError``
+    before any collective.  The ranks are taken to hold the same weights AND buffers: data-parallel replicas share their parameters,
+    not their BatchNorm running statistics (``step_amd.comm.broadcast_running_statistics`` hands rank 0's to every rank)."""
     from .step_arch.step import DeviceWindowLoader
+    if process_group is not None:
+        if getattr(model, "eval_noise", "position") != "window":
+            raise ValueError("STEP.evaluate(process_group=...): a pass spread over ranks needs eval_noise = \"window\" (positional noise "
+                             "depends on which rank evaluates which batch)")
+        if return_predictions:
+            raise ValueError("STEP.evaluate(process_group=...): return_predictions is not available for a pass spread over ranks")
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("step_amd.STEP runs only on an AMD GPU: libstep_hip has no CPU fallback")
@@ -163,11 +211,18 @@ def evaluate_pass(model, loader, origins=None, scaler=None, null_val=0.0, batch_
     H, N = loader.horizon, loader.data.shape[1]
     metrics = EvalMetrics(H, null_val, _scale_shift(scaler), device=dev)
     kept = torch.empty(len(origins), H, N, device=dev) if return_predictions else None
+    starts = list(range(0, len(origins), step))
+    if process_group is not None:
+        import torch.distributed as dist
+        seed = [model.eval_seed() if dist.get_rank(process_group) == 0 else None]
+        dist.broadcast_object_list(seed, src=dist.get_global_rank(process_group, 0), group=process_group)          # rank 0's eval seed
+        starts = [starts[c] for c in eval_rank_chunks(len(starts), dist.get_rank(process_group), dist.get_world_size(process_group))]
+        seed_before, model._eval_seed_override = model._eval_seed_override, int(seed[0])
     was_training = model.training
     model.eval()
     try:
         with torch.no_grad():
-            for at in range(0, len(origins), step):
+            for at in starts:
                 hist, ref, fut = loader.batch(origins[at:at + step])
                 pred = model(history_data=hist, long_history_data=ref, future_data=None, batch_seen=None, epoch=None)[0]
                 metrics.update(pred, fut[..., int(target_channel)])
@@ -175,5 +230,9 @@ def evaluate_pass(model, loader, origins=None, scaler=None, null_val=0.0, batch_
                     kept[at:at + pred.shape[0]].copy_(pred[..., 0])
     finally:
         model.train(was_training)
+        if process_group is not None:
+            model._eval_seed_override = seed_before
+    if process_group is not None:
+        metrics.all_reduce(process_group)
     res = metrics.result(horizons)
     return (res, kept) if return_predictions else res

@@ -230,9 +230,21 @@ class LookaheadLoader:
         self._copy_stream = None
         self.staged_batches = 0
         self.prefetched_batches = 0
+        # (rank, world) of an evaluation pass spread over ranks (native_runner(spread_eval=True)): only the batches
+        # ``eval_rank_chunks`` gives this rank are staged and handed out -- selected BEFORE staging, each with the composition it has
+        # in the whole pass (a coalesced batch is one chunk).  None: every batch
+        self.share = None
+
+    def total_batches(self):
+        """batches of the whole pass, whoever evaluates them"""
+        return -(-len(self.loader) // self.coalesce)
 
     def __len__(self):
-        return -(-len(self.loader) // self.coalesce)
+        n = self.total_batches()
+        if self.share is None:
+            return n
+        from .evaluate import eval_rank_chunks
+        return len(eval_rank_chunks(n, *self.share))
 
     @property
     def group_size(self):
@@ -287,6 +299,10 @@ class LookaheadLoader:
 
     def __iter__(self):
         it = iter(self.loader) if self.coalesce == 1 else coalesce_origin_batches(self.loader, self.coalesce)
+        if self.share is not None:
+            from .evaluate import eval_rank_chunks
+            mine = set(eval_rank_chunks(self.total_batches(), *self.share))
+            it = (batch for c, batch in enumerate(it) if c in mine)
         try:
             nxt = self._stage(next(it))
         except StopIteration:
@@ -350,7 +366,8 @@ class _Deferred:
 
 def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, encoder_workgroups=None, native_metrics=True,
                   eval_cache_bytes=0, native_tail=False, native_pretrain=False, native_data_parallel=False, replica_check=True,
-                  native_eval=False, eval_batch_size=None, accumulate=1, shard_graph_learner=False):
+                  native_eval=False, eval_batch_size=None, accumulate=1, shard_graph_learner=False, eval_noise="position",
+                  native_test=False, spread_eval=False):
     """-> subclass of ``base`` (the reference's ``STEPRunner``, or any ``BaseTimeSeriesForecastingRunner``) for ``CFG.RUNNER``.
     ``encoder_workgroups``: compute units of the persistent encoder launch next to the step (None: 160 at 307 nodes / 336 tokens, the
     measured optimum of config C2; 0: one workgroup per sequence) -- only used while batches are prefetched.
@@ -416,8 +433,38 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
     scheduler and the step count advance per optimizer step, the meters stay per iteration.  It needs the fused optimizer:
     ``init_training`` raises ``RuntimeError`` when ``accumulate > 1`` and ``FusedAdamClip`` was not swapped in (another optimizer, a
     module still wrapped, not a native module on a GPU) rather than train with another effective batch size.  Works with
-    ``native_tail``, ``native_pretrain`` and ``native_data_parallel`` (collectives on a group's last backward only)."""
+    ``native_tail``, ``native_pretrain`` and ``native_data_parallel`` (collectives on a group's last backward only).
+    ``eval_noise``: ``"window"`` sets ``STEP.eval_noise = "window"`` where the validation / test loaders are built: in eval mode the graph
+    learner's Gumbel noise is keyed by (edge, forecast origin of the window, one fixed seed) instead of (edge, position in the batch,
+    forward count), so a validation / test pass is a function of the weights and the windows alone -- the same for any
+    ``eval_batch_size``, with or without ``eval_cache_bytes``, on any number of ranks, and every epoch's ``val_MAE`` is drawn under the
+    same noise.  Needs index-only validation and test datasets (``DeviceForecastingDataset``: the origins are the keys); with anything
+    else rank 0 warns and the positional noise stays.  ``"position"`` (default): as the module does by itself.  Anything else:
+    ``ValueError``.
+    ``native_test``: the forecasting ``test()`` (``base_tsf_runner.py:277-318``: every prediction of the pass kept, concatenated,
+    rescaled and sliced per horizon) feeds every batch to one ``step_amd.EvalMetrics`` instead -- one launch per batch, nothing
+    concatenated, ONE read-back -- logs the reference's line for each of ``self.evaluation_horizons`` and sets ``test_MAE`` /
+    ``test_RMSE`` / ``test_MAPE`` from the table's overall row.  Under the conditions of ``native_eval`` (a ``STEP`` on a GPU, the
+    ``re_standard_transform`` scaler with scalar mean / std, only the three basicts metrics, a real ``null_val``); anything else takes
+    the base class's ``test()``.  The pre-training branch of ``test()`` is not affected.
+    ``spread_eval``: where ``native_data_parallel`` acts on a ``STEP``, the validation and the test pass of an epoch's end are spread
+    over the ranks instead of running on rank 0 while the others wait: batch ``c`` of a pass is evaluated by rank ``c % world``
+    (``step_amd.evaluate.eval_rank_chunks``), with the composition it has in the whole pass.  Rank 0 stays the master and runs the
+    reference's flow untouched (``validate``, ``test_process``, the meters, ``save_best_model``, ``save_model``) over its share; the
+    other ranks build their own validation / test loaders in ``init_training`` and run their share inside ``on_epoch_end``, for the
+    passes due this epoch (``VAL.INTERVAL`` / ``TEST.INTERVAL``), in eval mode under ``no_grad``.  Each pass has exactly ONE collective
+    per rank, ``EvalMetrics.all_reduce``: the meters rank 0 prints and the ``val_MAE`` ``save_best_model`` reads are those of the whole
+    pass.  In front of the passes of an epoch's end every rank takes rank 0's BatchNorm running statistics (one small broadcast,
+    ``step_amd.comm.broadcast_running_statistics``): the ranks' own drift apart with their batches, and the pass is rank 0's -- as
+    under ``DistributedDataParallel``, which hands rank 0's buffers to every rank.  It needs, on EVERY rank (one more word in the MIN all-reduce of ``init_training``; otherwise rank 0 warns and the passes
+    stay master-only): ``native_eval`` and ``native_test`` usable, index-only validation and test datasets, and
+    ``eval_noise="window"`` in effect -- only then is a pass the same whoever evaluates which batch.  Rank 0's eval seed is broadcast
+    once.  With ``shard_graph_learner`` acting the passes run behind the gather of the slices.  A validation forward whose outputs
+    do not qualify for ``EvalMetrics`` raises instead of taking the torch path (the other ranks would wait in the collective).
+    Without ``native_data_parallel``, or in a single process, the switch does nothing."""
     import operator
+    if eval_noise not in ("position", "window"):
+        raise ValueError(f"native_runner: eval_noise must be \"position\" or \"window\", got {eval_noise!r}")
     if isinstance(accumulate, (bool, float)) or operator.index(accumulate) < 1:
         raise ValueError(f"native_runner: accumulate must be an integer >= 1, got {accumulate!r}")
     accumulate = operator.index(accumulate)
@@ -433,6 +480,11 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             self._dp_acting = False          # native_data_parallel took the module out of its DistributedDataParallel wrap
             self._shard_acting = False          # ... and shard_graph_learner cut the graph learner in time slices
             self._val_metrics = None          # native_eval: (what it was built for, the validation pass's EvalMetrics)
+            self._eval_index_only = {}          # eval_noise: "val" / "test" -> the loader built here has an index-only dataset
+            self._eval_noise_warned = False
+            self._spread_acting = False          # spread_eval: the validation / test passes are spread over the ranks
+            self._helper_loaders = {}          # ... on a rank other than 0: its own "val" / "test" loaders
+            self.eval_readbacks = 0          # device-to-host copies of EvalMetrics tables (one per pass)
             self._group_size, self._group_pos = 1, 0          # accumulate: size of the open group, iterations of it that ran backward
 
         # ---------------------------------------------------------------- loaders
@@ -463,13 +515,38 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             k = 1 if isinstance(_unwrap(self.model), TSFormer) else coalesce_factor(eval_batch_size, loader)
             return LookaheadLoader(loader, self, prefetch=False, coalesce=k)
 
+        def _enable_eval_noise(self, which, loader):
+            """eval_noise="window": on the module once the loaders built so far all have index-only datasets (their origins are the keys)"""
+            model = _unwrap(self.model)
+            if eval_noise != "window" or not isinstance(model, STEP):
+                return
+            self._eval_index_only[which] = bool(getattr(getattr(loader, "dataset", None), "index_only", False))
+            ok = all(self._eval_index_only.values())
+            if not ok and not self._eval_noise_warned and self._rank_world()[0] == 0:
+                import warnings
+                self._eval_noise_warned = True
+                warnings.warn("step_amd.runner: eval_noise=\"window\" needs index-only validation and test datasets "
+                              "(DeviceForecastingDataset); the graph learner's eval noise stays positional")
+            model.eval_noise = "window" if ok else "position"
+
+        @staticmethod
+        def _rank_world():
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                return dist.get_rank(), dist.get_world_size()
+            return 0, 1
+
         def build_val_data_loader(self, cfg):
             self._enable_eval_cache()
-            return self._eval_lookahead(super().build_val_data_loader(cfg))
+            loader = self._eval_lookahead(super().build_val_data_loader(cfg))
+            self._enable_eval_noise("val", loader)
+            return loader
 
         def build_test_data_loader(self, cfg):
             self._enable_eval_cache()
-            return self._eval_lookahead(super().build_test_data_loader(cfg))
+            loader = self._eval_lookahead(super().build_test_data_loader(cfg))
+            self._enable_eval_noise("test", loader)
+            return loader
 
         # ---------------------------------------------------------------- feature selection without a host-device synchronisation
         # ``data[:, :, :, [0, 1, 2]]`` (step_runner.py:25-26,39-40) builds an index tensor on the host and copies it to the device: a blocking
@@ -515,7 +592,30 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             ok = (native_pretrain and isinstance(model, TSFormer) and model.mode == "pre-train" and next(model.parameters()).is_cuda)
             return model if ok else None
 
-        def _enable_data_parallel(self):
+        def _spread_loaders(self, cfg):
+            """this rank's validation and test loaders for a spread pass: rank 0's are the runner's own (init_validation / init_test are
+            master-only), the other ranks build theirs through the same hooks -> (val, test), None where there is none"""
+            if self._rank_world()[0] == 0:
+                return getattr(self, "val_data_loader", None), getattr(self, "test_data_loader", None)
+            for which, build in (("val", self.build_val_data_loader), ("test", self.build_test_data_loader)):
+                if which not in self._helper_loaders:
+                    try:
+                        self._helper_loaders[which] = build(cfg)
+                    except Exception:          # (a config without that pass, a missing file: this rank votes against)
+                        self._helper_loaders[which] = None
+            return self._helper_loaders.get("val"), self._helper_loaders.get("test")
+
+        def _spread_vote(self, cfg, model):
+            """this rank's vote on spread_eval: native_eval and native_test usable, index-only validation and test datasets behind the
+            look-ahead loader, eval_noise="window" in effect"""
+            if not (native_eval and native_test and eval_noise == "window" and isinstance(model, STEP) and self._eval_scaler() is not None):
+                return False
+            loaders = self._spread_loaders(cfg)
+            if not all(isinstance(ld, LookaheadLoader) and getattr(ld.dataset, "index_only", False) for ld in loaders):
+                return False
+            return model.eval_noise == "window"
+
+        def _enable_data_parallel(self, cfg=None):
             """native_data_parallel: the same decision on every rank, then unwrap and enable -> True when it acted"""
             import torch.distributed as dist
             if not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
@@ -532,9 +632,20 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                     model.matmul_precision, model.discrete_graph_learning.train_length - 18, dist.get_world_size(),
                     self._fused_swap_ok(model, getattr(self, "optim", None), False))
                 votes.append(1 if slices else 0)
+            if spread_eval:
+                # ... and the vote on the spread validation / test passes: no rank may wait in a pass's collective alone
+                votes.append(1 if (able and self._spread_vote(cfg, model)) else 0)
             every = torch.tensor(votes, dtype=torch.int32, device=dev)
             dist.all_reduce(every, op=dist.ReduceOp.MIN)
             every = every.tolist()
+            spread = bool(spread_eval and every[0] == 1 and every[-1] == 1)
+            if spread_eval and not spread:
+                self._helper_loaders = {}
+                if dist.get_rank() == 0:
+                    import warnings
+                    warnings.warn("step_amd.runner: spread_eval needs, on every rank, native_data_parallel acting on a STEP, native_eval and "
+                                  "native_test usable, index-only validation and test datasets and eval_noise=\"window\"; the validation "
+                                  "and test passes stay on rank 0")
             if every[0] == 0:
                 if dist.get_rank() == 0:
                     import warnings
@@ -558,9 +669,22 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                 # (after the resume: the slice is cut from the resumed, broadcast fc.weight)
                 model.enable_native_data_parallel(collectives="auto", sync_module_states=True, shard_graph_learner=True)
                 self._shard_acting = True
-                return True
-            model.enable_native_data_parallel(collectives="auto", sync_module_states=True)          # (after the resume: resumed weights are broadcast)
+            else:
+                model.enable_native_data_parallel(collectives="auto", sync_module_states=True)          # (after the resume: resumed weights are broadcast)
+            if spread:
+                self._enable_spread(cfg, model)
             return True
+
+        def _enable_spread(self, cfg, model):
+            """every rank, after the vote: this rank's share on its loaders, rank 0's eval seed everywhere (one broadcast)"""
+            import torch.distributed as dist
+            rank, world = dist.get_rank(), dist.get_world_size()
+            for loader in self._spread_loaders(cfg):
+                loader.share = (rank, world)
+            seed = [model.eval_seed() if rank == 0 else None]
+            dist.broadcast_object_list(seed, src=0)
+            model._eval_seed_override = int(seed[0])
+            self._spread_acting = True
 
         def init_training(self, cfg):
             if native_data_parallel and shard_graph_learner and accumulate > 1:
@@ -568,7 +692,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                 raise ValueError(f"step_amd.runner: shard_graph_learner=True cannot be combined with accumulate={accumulate}: a time-sliced "
                                  "graph learner takes one backward per optimizer step (set accumulate=1, or shard_graph_learner=False)")
             super().init_training(cfg)
-            self._dp_acting = self._enable_data_parallel() if native_data_parallel else False
+            self._dp_acting = self._enable_data_parallel(cfg) if native_data_parallel else False
             model = _unwrap(self.model)
             opt = getattr(self, "optim", None)
             pretrain = self._pretrain_module() is not None
@@ -721,8 +845,10 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
         def _eval_scaler(self):
             """(mean, std) when everything known BEFORE the forward pass allows the validation meters to come from ``EvalMetrics``,
             else None.  The loss plays no part in a validation pass, and ``null_val`` may be NaN (the reference's default)"""
-            if not native_eval:
-                return None
+            return self._eval_conditions() if native_eval else None
+
+        def _eval_conditions(self):
+            """what ``native_eval`` and ``native_test`` ask for, apart from their switches -> (mean, std) or None"""
             model = _unwrap(self.model)
             if not (isinstance(model, STEP) and next(model.parameters()).is_cuda):
                 return None
@@ -746,21 +872,33 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             m = self._val_metrics[1] if self._val_metrics is not None else None
             if m is None or m.batches == 0:
                 return
+            if self._spread_acting:
+                # the pass's one collective (rank 0 owns batch 0: it is here whenever the pass has a batch; the others: _helper_passes)
+                m.all_reduce(_unwrap(self.model)._process_group)
             res = m.result()
+            self.eval_readbacks += 1
             for metric_name, metric_func in self.metrics.items():
                 super().update_epoch_meter("val_" + metric_name, float(res.batch_mean[self._NATIVE_METRICS[metric_func.__name__]]), n=res.batches)
             m.reset()
 
-        def _native_eval_iters(self, data, scaler):
-            """base_tsf_runner.py:257-273 with the rescaling and the three metrics in one ``EvalMetrics.update``, nothing read back"""
+        @staticmethod
+        def _qualifies(pred, real):
+            """the forward's outputs are what ``EvalMetrics.update`` takes"""
             from .evaluate import MAX_HORIZONS
+            return (torch.is_tensor(pred) and torch.is_tensor(real) and pred.is_cuda and real.is_cuda and pred.device == real.device
+                    and pred.dtype == torch.float32 and real.dtype == torch.float32 and pred.dim() == 4 and pred.shape[3] == 1
+                    and pred.shape == real.shape and 0 not in pred.shape and pred.shape[1] <= MAX_HORIZONS
+                    and all(st > 0 for t in (pred, real) for size, st in zip(t.shape, t.stride()) if size > 1))
+
+        def _native_eval_iters(self, data, scaler, loader=None):
+            """base_tsf_runner.py:257-273 with the rescaling and the three metrics in one ``EvalMetrics.update``, nothing read back"""
             mean, std = scaler
             forward_return = self.forward(data=data, epoch=None, iter_num=None, train=False)
             pred, real = forward_return[0], forward_return[1]
-            ok = (torch.is_tensor(pred) and torch.is_tensor(real) and pred.is_cuda and real.is_cuda and pred.device == real.device
-                  and pred.dtype == torch.float32 and real.dtype == torch.float32 and pred.dim() == 4 and pred.shape[3] == 1
-                  and pred.shape == real.shape and 0 not in pred.shape and pred.shape[1] <= MAX_HORIZONS
-                  and all(st > 0 for t in (pred, real) for size, st in zip(t.shape, t.stride()) if size > 1))
+            ok = self._qualifies(pred, real)
+            if not ok and self._spread_acting:
+                raise RuntimeError("step_amd.runner: a validation forward whose outputs EvalMetrics cannot take, in a pass spread over the "
+                                   "ranks (spread_eval): the torch path would leave the other ranks waiting in the pass's collective")
             if not ok:
                 # the forward pass is done and cannot be repeated: the base class's tail (:267-273) on torch ops, the scaler being
                 # re_standard_transform with scalar mean / std (basicts/data/transform.py:59-65)
@@ -769,7 +907,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                     metric_item = self.metric_forward(metric_func, [prediction_rescaled, real_value_rescaled])
                     self.update_epoch_meter("val_" + metric_name, metric_item.item())
                 return
-            loader = getattr(self, "val_data_loader", None)
+            loader = getattr(self, "val_data_loader", None) if loader is None else loader
             group = loader.group_size if isinstance(loader, LookaheadLoader) and loader.coalesce > 1 else None
             self._val_accumulator(pred.shape[1], mean, std, pred.device).update(pred, real, group=group)
 
@@ -803,9 +941,15 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
 
         def test(self, *args, **kwargs):
             """``TSFormerRunner.test`` (step/step_runner/tsformer_runner.py:73-90) under ``native_pretrain``: one ``pretrain_tail`` call per
-            batch, the three ``test_`` meters queued on the device like the validation ones.  Every other runner's ``test()`` is its own"""
+            batch, the three ``test_`` meters queued on the device like the validation ones.  A forecasting runner's ``test()`` under
+            ``native_test``: ``_native_test`` (one ``EvalMetrics`` per pass).  Every other runner's ``test()`` is its own"""
             if self._pretrain_module() is None:
-                return super().test(*args, **kwargs)
+                scaler = self._eval_conditions() if native_test else None
+                if scaler is None:
+                    return super().test(*args, **kwargs)
+                if self._rank_world()[0] != 0:
+                    return None          # (the reference's test() is master_only; the other ranks of a spread pass: _helper_passes)
+                return self._native_test(scaler, self.test_data_loader, lambda: super(NativeRunner, self).test(*args, **kwargs))
             import torch.distributed as dist
             if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
                 return None          # (the reference's test() is master_only)
@@ -822,6 +966,75 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                         self.update_epoch_meter("test_" + metric_name, _Deferred(three[self._NATIVE_METRICS[metric_func.__name__]]))
                     data = next(batches, None)
             return None
+
+        # ---------------------------------------------------------------- the forecasting test pass on the device (native_test=True)
+        def _native_test(self, scaler, loader, base_test=None):
+            """base_tsf_runner.py:277-318 from one ``EvalMetrics``: one accumulate launch per batch on the normalised prediction and the
+            batch's target view, nothing kept, one read-back; then the reference's line per evaluation horizon and the three ``test_``
+            meters from the overall row.  ``base_test``: what to run instead when the FIRST forward's outputs do not qualify (rank 0 of
+            an unspread pass only; that batch is then forwarded twice).  On a rank other than 0 (a spread pass) nothing is logged"""
+            from .evaluate import EvalMetrics
+            mean, std = scaler
+            rank = self._rank_world()[0]
+            m = None
+            with torch.no_grad():
+                for data in loader:
+                    forward_return = self.forward(data, epoch=None, iter_num=None, train=False)
+                    pred, real = forward_return[0], forward_return[1]
+                    if not self._qualifies(pred, real):
+                        if m is None and base_test is not None and not self._spread_acting:
+                            return base_test()
+                        raise RuntimeError("step_amd.runner: native_test met a forward whose outputs EvalMetrics cannot take "
+                                           f"(prediction {tuple(getattr(pred, 'shape', ()))}, {getattr(pred, 'dtype', type(pred))})")
+                    if m is None:
+                        m = EvalMetrics(pred.shape[1], float(self.null_val), rescale=(std, mean), device=pred.device)
+                    m.update(pred, real)
+            if self._spread_acting:
+                if m is None and loader.total_batches() > 0:          # a rank without a batch of its own still answers the collective
+                    H = int(getattr(loader.dataset, "future_len", 12))
+                    m = EvalMetrics(H, float(self.null_val), rescale=(std, mean), device=next(_unwrap(self.model).parameters()).device)
+                if m is not None:
+                    m.all_reduce(_unwrap(self.model)._process_group)          # the pass's one collective
+            if m is None or rank != 0:
+                return None
+            res = m.result()
+            self.eval_readbacks += 1
+            names = [(metric_name, self._NATIVE_METRICS[metric_func.__name__]) for metric_name, metric_func in self.metrics.items()]
+            for i in self.evaluation_horizons:
+                metric_repr = ""
+                for metric_name, k in names:
+                    metric_repr += ", Test {0}: {1:.4f}".format(metric_name, float(res.per_horizon[i][k]))
+                log = "Evaluate best model on test data for horizon {:d}" + metric_repr
+                self.logger.info(log.format(i + 1))
+            for metric_name, k in names:
+                super().update_epoch_meter("test_" + metric_name, float(res.overall[k]))
+            return None
+
+        # ---------------------------------------------------------------- a rank other than 0 in spread validation / test passes
+        def _helper_passes(self, epoch):
+            """this rank's share of the passes due at the end of ``epoch`` (the arithmetic of base_runner.py:143-148), in rank 0's order:
+            validation, then test -- each ends in the pass's one collective"""
+            model = _unwrap(self.model)
+            scaler = self._eval_scaler()
+            if scaler is None:
+                raise RuntimeError("step_amd.runner: spread_eval is acting but native_eval is no longer usable on this rank")
+            mean, std = scaler
+            val, test = self._helper_loaders["val"], self._helper_loaders["test"]
+            was_training = model.training
+            model.eval()
+            try:
+                with torch.no_grad():
+                    if epoch % int(getattr(self, "val_interval", 1)) == 0 and val.total_batches() > 0:
+                        for data in val:
+                            self._native_eval_iters(data, scaler, loader=val)
+                        dev = next(model.parameters()).device
+                        m = self._val_accumulator(int(getattr(val.dataset, "future_len", 12)), mean, std, dev)
+                        m.all_reduce(model._process_group)
+                        m.reset()          # (the table is rank 0's to read)
+                    if epoch % int(getattr(self, "test_interval", 1)) == 0:
+                        self._native_test(scaler, test)
+            finally:
+                model.train(was_training)
 
         def _native_tail_iters(self, epoch, iter_index, data, scaler):
             """base_tsf_runner.py:237-255 with the rescaling, the curriculum slice, the loss and the three metrics in one train_tail call"""
@@ -928,7 +1141,22 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             def on_epoch_end(self, *args, **kwargs):
                 """``basicts/runners/base_runner.py:132-152`` runs on every rank and calls the master-only ``validate``, ``test_process``
                 and ``save_model``: the slices are gathered in front of it, the staging is released behind it"""
-                return self._with_gathered_slices(super().on_epoch_end, *args, **kwargs)
+                return self._with_gathered_slices(self._epoch_end, *args, **kwargs)
+
+            def _epoch_end(self, *args, **kwargs):
+                if self._spread_acting:
+                    epoch = int(args[0] if args else kwargs["epoch"])
+                    if epoch % int(getattr(self, "val_interval", 1)) == 0 or epoch % int(getattr(self, "test_interval", 1)) == 0:
+                        # every rank evaluates under rank 0's BatchNorm running statistics, as the master-only passes do (the ranks'
+                        # own drift apart with their batches): one small broadcast per epoch's end, in front of the passes
+                        from .comm import broadcast_running_statistics
+                        model = _unwrap(self.model)
+                        broadcast_running_statistics(model, model._process_group)
+                        if self._rank_world()[0] != 0:
+                            model._drop_eval_g()          # (a kept global feature was computed under the statistics just replaced)
+                            # (the base class's validate / test_process / save_model are master-only: nothing of them runs here)
+                            self._helper_passes(epoch)
+                return super().on_epoch_end(*args, **kwargs)
         elif hasattr(base, "save_model"):
             def save_model(self, *args, **kwargs):
                 """a base without ``on_epoch_end``: the same in front of ``save_model``, which every rank has to call"""

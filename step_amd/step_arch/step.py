@@ -114,6 +114,9 @@ class _StepFunction(torch.autograd.Function):
         ec_on, model._ec_on = model._ec_on, False
         # gradient accumulation (STEP.set_grad_accumulation): the open group of a training forward that takes gradients; None for k = 1
         acc_fwd, model._acc_fwd = model._acc_fwd, False
+        key = model._noise_key          # eval_noise = "window" (STEP.forward set it for this call): the noise is keyed by these origins
+        if key is not None:
+            model._noise_key = None
         ec = model._eval_cache_plan(long_hist, N, Lh // 12, dev) if ec_on else None
         # Everything up to the GraphWaveNet head is independent of the (frozen) TSFormer: the DGL's global feature, the edge
         # logits, the Gumbel sample and the 8 WaveNet layers only need the train series, the short history and the weights.
@@ -164,7 +167,9 @@ class _StepFunction(torch.autograd.Function):
         wsaved = _f32(L.lib().step_gwnet_saved_floats(B, N, int(drop > 0)), dev)
         wwork = _f32(L.lib().step_gwnet_work_floats(B, N, 0), dev)
         pred = _f32(B * 12 * N, dev).view(B, 12, N)
-        seed, seed_gw = model._next_seed(), model._next_seed()
+        seed, seed_gw = model._next_seed(), model._next_seed()          # (the counter advances under either eval_noise)
+        if key is not None:
+            seed = model.eval_seed()
         side = model._side_stream(dev) if model.overlap_streams else None
         main = torch.cuda.current_stream()
         if side is not None:
@@ -203,8 +208,12 @@ class _StepFunction(torch.autograd.Function):
                            L.ptr(gsaved), L.ptr(gwork), L.ptr(sums), L.ptr(g), ctypes.byref(sstruct), phase, sst)
                     if phase in exchange:
                         model._sum_over_ranks(exchange[phase])
-            L.call("step_dgl_edges_forward_dyn", L.ptr(g), N, B, ctypes.byref(dstruct), L.ptr(u) if u is not None else None, seed,
-                   TEMPERATURE, L.ptr(esaved), L.ptr(theta), L.ptr(adj), L.ptr(model._dyn), sst)
+            if key is not None:
+                L.call("step_dgl_edges_forward_keyed", L.ptr(g), N, B, ctypes.byref(dstruct), L.ptr(key), seed,
+                       TEMPERATURE, L.ptr(esaved), L.ptr(theta), L.ptr(adj), sst)
+            else:
+                L.call("step_dgl_edges_forward_dyn", L.ptr(g), N, B, ctypes.byref(dstruct), L.ptr(u) if u is not None else None, seed,
+                       TEMPERATURE, L.ptr(esaved), L.ptr(theta), L.ptr(adj), L.ptr(model._dyn), sst)
             if prep_done is not None:
                 torch.cuda.current_stream().wait_event(prep_done)
             L.call("step_gwnet_forward_phase_dyn", L.ptr(hist), B, N, Cin, None, L.ptr(adj), ctypes.byref(bstruct),
@@ -234,6 +243,8 @@ class _StepFunction(torch.autograd.Function):
                     hist.record_stream(side)
                     if u is not None:
                         u.record_stream(side)
+                    if key is not None:
+                        key.record_stream(side)
                     graph_and_layers(L.stream())
             except BaseException:
                 # the join is queued even when a launch above raised: buffers handed back to the allocator must not be
@@ -483,6 +494,16 @@ class STEP(nn.Module):
         self.track_dead_bn7 = False
         self._noise_override = None         # tests: explicit uniform noise [B, N*N, 2]
         self._seed_ctr = 0
+        # The graph learner samples in eval mode too.  "position" (default): its device noise is keyed by (edge, position in the batch,
+        # a seed that advances with every forward) -- a window's graph depends on where in which batch it sits and on how many forwards
+        # came before.  "window": in eval mode the noise is keyed by (edge, forecast origin of the window, one fixed seed), so that a
+        # validation / test pass is a function of the weights and the windows alone: the same for any batch size, order, number of
+        # ranks, with or without the evaluation cache, pass after pass (step_dgl_edges_forward_keyed).  Needs a LongHistoryRef (its t0
+        # is the key, read on the device).  Training forwards, _noise_override and gumbel_noise = "torch_cpu" are not affected.
+        self.eval_noise = "position"
+        self.eval_noise_seed = 0            # selects the fixed stream of eval_noise = "window" (with torch.initial_seed())
+        self._eval_seed_override = None     # a pass spread over ranks: rank 0's eval seed (evaluate_pass / the runner)
+        self._noise_key = None              # forward() -> _StepFunction.forward: int64 [B] device keys of this call's noise
         self._dyn = None                    # device StepDynState of a replayed (graph-captured) step (step_amd/graphed.py); None: eager
         self._process_group = None
         self._struct_cache = {}             # (bf16 flag, full) -> (address key, StepDglParams, StepGwnetParams), see _param_structs
@@ -926,6 +947,26 @@ class STEP(nn.Module):
         self._seed_ctr += 1
         return (torch.initial_seed() * 2654435761 + self._seed_ctr * 40503) & ((1 << 63) - 1)
 
+    def _window_keys(self, long_history_data, u):
+        """eval_noise other than the default: the int64 device keys of this forward's noise -- the forecast origins, for an eval-mode
+        forward on the device's own noise -- or None (a training forward, explicit or host noise: the switch is ignored)"""
+        if self.eval_noise != "window":
+            raise ValueError(f"STEP.eval_noise = {self.eval_noise!r}: expected \"position\" or \"window\"")
+        if self.training or u is not None:
+            return None
+        if not isinstance(long_history_data, LongHistoryRef):
+            raise ValueError("STEP.eval_noise = \"window\" keys the graph learner's noise by the forecast origins of a LongHistoryRef: "
+                             "feed the model from a DeviceWindowLoader / DeviceForecastingDataset (a plain long-history tensor "
+                             "carries no origins; positional noise is not substituted)")
+        return long_history_data.t0
+
+    def eval_seed(self):
+        """the fixed seed of eval_noise = "window": like _next_seed, from eval_noise_seed instead of the counter (or the seed another
+        rank handed over for a pass spread over ranks)"""
+        if self._eval_seed_override is not None:
+            return int(self._eval_seed_override)
+        return (torch.initial_seed() * 2654435761 + int(self.eval_noise_seed) * 40503 + 0x5EEE) & ((1 << 63) - 1)
+
     def _trainable(self):
         items = [("be." + k, v) for k, v in self.backend.trainable_native().items()]
         items += [("dgl." + k, v) for k, v in self.discrete_graph_learning.trainable_native().items()]
@@ -1198,6 +1239,8 @@ class STEP(nn.Module):
             u = torch.rand(B, N * N, 2).to(history_data.device)
         else:
             u = None
+        if self.eval_noise != "position":          # (the default path pays this one comparison)
+            self._noise_key = self._window_keys(long_history_data, u)
         params = self._trainable_list()
         self._ec_on = self.eval_cache_bytes > 0 and self._eval_cache_active()
         self._acc_fwd = self.training and torch.is_grad_enabled()
@@ -1210,9 +1253,10 @@ class STEP(nn.Module):
 
     # ------------------------------------------------------------------ validation / test pass
     def evaluate(self, loader, origins=None, scaler=None, null_val=0.0, batch_size=None, target_channel=0, horizons=None,
-                 return_predictions=False):
+                 return_predictions=False, process_group=None):
         """One validation / test pass over a device-resident series with the reference's masked MAE / RMSE / MAPE per horizon, overall
-        and per batch accumulated on the device and read back once: ``step_amd.evaluate.evaluate_pass`` (documented there)."""
+        and per batch accumulated on the device and read back once: ``step_amd.evaluate.evaluate_pass`` (documented there).
+        ``process_group``: the pass spread over the ranks of a ``torch.distributed`` group (needs ``eval_noise == "window"``)."""
         from ..evaluate import evaluate_pass
         return evaluate_pass(self, loader, origins, scaler=scaler, null_val=null_val, batch_size=batch_size, target_channel=target_channel,
-                             horizons=horizons, return_predictions=return_predictions)
+                             horizons=horizons, return_predictions=return_predictions, process_group=process_group)
