@@ -564,10 +564,16 @@ int step_frozen_cache_load(const float* cache_last, const uint32_t* cache_bits, 
  *               MAPE: y0 = |y| < 1e-4 ? 0 : y, m0 = !(|y0| <= 5e-5), sum |(|p - y0|) / y0| / sum m0; a count of 0 gives 0
  *  out          f64 [(H + 2) * 3] = {MAE, RMSE, MAPE} of horizon h at 3 h; of all horizons at 3 H; at 3 (H + 1) the equal-weight mean
  *               over the _accumulate calls of each call's own overall metrics (what the validation meters average)
+ *  _nodes       the same accumulation under a per-node scaler (a data set prepared with --norm_each_channel: mean and std of shape
+ *               [1, N, 1]): scale_n, shift_n f32 [N] on the device, element (b, h, n) is taken on x * scale_n[n] + shift_n[n], rounded
+ *               twice as above.  Same accumulator, same null_val rule; calls of both forms may feed one accumulator
  * H <= 64, B * N < 2^31.  One launch per call. */
 long step_eval_metrics_acc_doubles(int H);          /* 0 for H < 1 or H > 64; pure host function */
 int step_eval_metrics_accumulate(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh, long r_sn,
                                  int B, int H, int N, float scale, float shift, float null_val, double* acc, void* stream);
+int step_eval_metrics_accumulate_nodes(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh, long r_sn,
+                                       int B, int H, int N, const float* scale_n, const float* shift_n, float null_val, double* acc,
+                                       void* stream);
 int step_eval_metrics_finish(const double* acc, int H, double* out, void* stream);
 
 /* ---------------------------------------------------------------- training tail -----------
@@ -582,17 +588,24 @@ int step_eval_metrics_finish(const double* acc, int H, double* out, void* stream
  *  work         f64 [step_train_tail_work_doubles()], zero before the FIRST call, then left to the calls of ONE stream: two halves of
  *               six sums {S_abs, S_sq, cnt, S_ape, cnt0, S_bce} used by alternate calls (a call's second launch clears the half of the
  *               next call: no memset is queued) and the call index
- *  loss         f32 [1] = S_abs / cnt + coef * S_bce / n_adj, m = !(|y - null_val| <= 5e-5) (null_val finite); cnt == 0 leaves the
- *               graph term
+ *  loss         f32 [1] = S_abs / cnt + coef * S_bce / n_adj, m = !(|y - null_val| <= 5e-5), or !isnan(y) for a NaN null_val (the
+ *               reference's default; an infinite null_val is refused); cnt == 0 leaves the graph term
  *  metrics      f32 [3] = MAE, RMSE, MAPE with the definitions of step_eval_metrics_accumulate (a NaN term adds 0 and still counts)
  *  dpred        f32 [B * H * N] contiguous, ALL of it written: sign(p - y) * scale / cnt at included, unmasked elements; exactly 0 at
  *               excluded horizons, masked labels and NaN differences
  *  dtheta       f32 [n_adj] = coef / n_adj * (theta - prior) / max(theta (1 - theta), 1e-12)
+ *  _nodes       the same tail under a per-node scaler (mean and std of shape [1, N, 1]): scale_n, shift_n f32 [N] on the device, the
+ *               terms are taken on x * scale_n[n] + shift_n[n], dpred = sign(p - y) * scale_n[n] / cnt.  Same work buffer (the two forms
+ *               may alternate on one stream), same null_val rule (additive to ABI 10)
  * B * H * N < 2^31. */
 long step_train_tail_work_doubles(void);          /* pure host function */
 int step_train_tail(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh, long r_sn, int B, int H,
                     int N, int k, float scale, float shift, float null_val, const float* theta, const float* prior, long n_adj, float coef,
                     double* work, float* loss, float* metrics, float* dpred, float* dtheta, void* stream);
+int step_train_tail_nodes(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh, long r_sn, int B,
+                          int H, int N, int k, const float* scale_n, const float* shift_n, float null_val, const float* theta,
+                          const float* prior, long n_adj, float coef, double* work, float* loss, float* metrics, float* dpred,
+                          float* dtheta, void* stream);
 
 /* ---------------------------------------------------------------- pre-training tail -------
  * The tail of one TSFormer pre-training iteration in two launches: masked_mae (basicts/metrics/mae.py) on the RESCALED reconstruction of
@@ -608,7 +621,8 @@ int step_train_tail(const float* pred, long p_sb, long p_sh, long p_sn, const fl
  *               the terms are taken on x * scale + shift, rounded twice as torch does
  *  work         f64 [step_pretrain_tail_work_doubles()], zero before the FIRST call, then left to the calls of ONE stream (the scheme
  *               of step_train_tail: two halves used by alternate calls, no memset is queued)
- *  loss         f32 [1] = S_abs / cnt, m = !(|y - null_val| <= 5e-5) (null_val finite); 0 when cnt == 0
+ *  loss         f32 [1] = S_abs / cnt, m = !(|y - null_val| <= 5e-5), or !isnan(y) for a NaN null_val (an infinite one is refused);
+ *               0 when cnt == 0
  *  metrics      f32 [3] = MAE, RMSE, MAPE with the definitions of step_eval_metrics_accumulate (a NaN term adds 0 and still counts)
  *  dr           f32 [S, P, 12], ALL of it written: sign(p - y) * scale / cnt at the counted elements of the masked rows; exactly 0 in
  *               rows < Pu, at masked labels and at NaN differences.  NULL: the values only (validation)

@@ -167,10 +167,12 @@ _SIGS = {
     # per-horizon evaluation metrics of a whole pass (csrc/eval_metrics.hip)
     "step_eval_metrics_acc_doubles": (_l, [_i]),
     "step_eval_metrics_accumulate": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _f, _f, _f, _vp, _vp]),
+    "step_eval_metrics_accumulate_nodes": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _vp, _vp, _f, _vp, _vp]),
     "step_eval_metrics_finish": (_i, [_vp, _i, _vp, _vp]),
     # loss, gradients and meters of a training iteration on the first k horizons (csrc/train_tail.hip)
     "step_train_tail_work_doubles": (_l, []),
     "step_train_tail": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _l, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "step_train_tail_nodes": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _l, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     # loss, gradient and meters of a pre-training iteration from the decoder's output and the packed series (csrc/pretrain_tail.hip)
     "step_pretrain_tail_work_doubles": (_l, []),
     "step_pretrain_tail": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),

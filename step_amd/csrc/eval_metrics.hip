@@ -11,6 +11,7 @@
 // Calls on one accumulator must be ordered by their stream: the per-call slots belong to one launch at a time.
 #include "common.h"
 #include <limits.h>
+#include <type_traits>
 
 namespace {
 
@@ -22,12 +23,17 @@ constexpr int EM_GRID_TARGET = 384;      // workgroups of one launch: H * chunks
 
 __host__ __device__ inline long em_acc_doubles(int H) { return (long)EM_SUMS * H + EM_SUMS + 3 + 1 + 1; }
 
+// NODES = false: one scale and one shift (float); true: f32 [N] of each on the device, read at the element's node -- two instantiations
+// of the kernel, nothing is chosen per element
+template <bool NODES>
 struct MetricArgs {
+    using Scaler = std::conditional_t<NODES, const float*, float>;
     const float* pred; long p_sb, p_sh, p_sn;
     const float* real; long r_sb, r_sh, r_sn;
     int B, H, N;
     unsigned per_h;            // B * N elements of one horizon
-    float scale, shift, null_val;
+    Scaler scale, shift;
+    float null_val;
     int null_is_nan;
     double* acc;
 };
@@ -43,7 +49,8 @@ __device__ __forceinline__ double slot_value(double* p) { return atomicAdd(p, 0.
 // through LDS; lanes 0..4 then add the workgroup's five sums to the horizon's slots and to the call's.  Those ten atomics RETURN their old
 // values into LDS, so they have been performed when the barrier behind them is passed and the ticket is drawn; the workgroup that draws
 // the last ticket turns the call's sums into the call's three metrics and clears the per-call slots for the next launch.
-__global__ __launch_bounds__(EM_THREADS) void eval_metrics_kernel(MetricArgs a) {
+template <bool NODES>
+__global__ __launch_bounds__(EM_THREADS) void eval_metrics_kernel(MetricArgs<NODES> a) {
     // The rescaling must round twice, like torch's `x * std + mean`: a label ONE float32 step across the 5e-5 / 1e-4 thresholds changes its
     // mask, and its MAPE term by tens of percent.  hipcc contracts a * b + c into one fma by default -- also through __fmul_rn / __fadd_rn,
     // which are plain `*` / `+` carrying the header's contraction flag -- so the arithmetic below is written with operators and
@@ -59,8 +66,10 @@ __global__ __launch_bounds__(EM_THREADS) void eval_metrics_kernel(MetricArgs a) 
     const unsigned step = gridDim.x * EM_THREADS;
     for (unsigned i = blockIdx.x * EM_THREADS + threadIdx.x; i < a.per_h; i += step) {
         const unsigned b = i / (unsigned)a.N, n = i - b * (unsigned)a.N;
-        const float p = pred[(long)b * a.p_sb + (long)n * a.p_sn] * a.scale + a.shift;
-        const float y = real[(long)b * a.r_sb + (long)n * a.r_sn] * a.scale + a.shift;
+        float scale, shift;
+        if constexpr (NODES) { scale = a.scale[n]; shift = a.shift[n]; } else { scale = a.scale; shift = a.shift; }
+        const float p = pred[(long)b * a.p_sb + (long)n * a.p_sn] * scale + shift;
+        const float y = real[(long)b * a.r_sb + (long)n * a.r_sn] * scale + shift;
         // mae.py:17-21 / rmse.py:17-21: ~isnan(y), or ~isclose(y, null, atol = 5e-5, rtol = 0) -- a NaN label is not close to a finite null
         const bool m = a.null_is_nan ? !isnan(y) : !(fabsf(y - a.null_val) <= 5e-5f);
         if (m) {
@@ -131,18 +140,20 @@ __global__ __launch_bounds__(128) void eval_metrics_finish_kernel(const double* 
 
 extern "C" long step_eval_metrics_acc_doubles(int H) { return H < 1 || H > EM_MAX_H ? 0 : em_acc_doubles(H); }
 
-extern "C" int step_eval_metrics_accumulate(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh,
-                                            long r_sn, int B, int H, int N, float scale, float shift, float null_val, double* acc,
-                                            void* stream) {
-    STEP_REQUIRE(pred && real && acc, "eval_metrics_accumulate: NULL pred, real or acc");
-    STEP_REQUIRE(B > 0 && H > 0 && N > 0, "eval_metrics_accumulate: B = %d, H = %d, N = %d must all be positive", B, H, N);
-    STEP_REQUIRE(H <= EM_MAX_H, "eval_metrics_accumulate: H = %d exceeds the %d horizons of one accumulator", H, EM_MAX_H);
+namespace {
+
+template <bool NODES>
+int eval_metrics_launch(const char* op, const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh, long r_sn,
+                        int B, int H, int N, typename MetricArgs<NODES>::Scaler scale, typename MetricArgs<NODES>::Scaler shift, float null_val,
+                        double* acc, void* stream) {
+    STEP_REQUIRE(pred && real && acc, "%s: NULL pred, real or acc", op);
+    if constexpr (NODES) STEP_REQUIRE(scale && shift, "%s: NULL scale_n or shift_n", op);
+    STEP_REQUIRE(B > 0 && H > 0 && N > 0, "%s: B = %d, H = %d, N = %d must all be positive", op, B, H, N);
+    STEP_REQUIRE(H <= EM_MAX_H, "%s: H = %d exceeds the %d horizons of one accumulator", op, H, EM_MAX_H);
     STEP_REQUIRE(p_sb > 0 && p_sh > 0 && p_sn > 0 && r_sb > 0 && r_sh > 0 && r_sn > 0,
-                 "eval_metrics_accumulate: element strides must be positive (pred %ld, %ld, %ld; real %ld, %ld, %ld)", p_sb, p_sh, p_sn, r_sb,
-                 r_sh, r_sn);
-    STEP_REQUIRE((long)B * N <= INT_MAX, "eval_metrics_accumulate: B * N = %ld exceeds the %d elements per horizon of one launch", (long)B * N,
-                 INT_MAX);
-    MetricArgs a;
+                 "%s: element strides must be positive (pred %ld, %ld, %ld; real %ld, %ld, %ld)", op, p_sb, p_sh, p_sn, r_sb, r_sh, r_sn);
+    STEP_REQUIRE((long)B * N <= INT_MAX, "%s: B * N = %ld exceeds the %d elements per horizon of one launch", op, (long)B * N, INT_MAX);
+    MetricArgs<NODES> a;
     a.pred = pred; a.p_sb = p_sb; a.p_sh = p_sh; a.p_sn = p_sn;
     a.real = real; a.r_sb = r_sb; a.r_sh = r_sh; a.r_sn = r_sn;
     a.B = B; a.H = H; a.N = N; a.per_h = (unsigned)((long)B * N);
@@ -152,9 +163,25 @@ extern "C" int step_eval_metrics_accumulate(const float* pred, long p_sb, long p
     int chunks = cdiv(a.per_h, 4 * EM_THREADS);
     const int most = EM_GRID_TARGET / H > 1 ? EM_GRID_TARGET / H : 1;
     chunks = chunks < 1 ? 1 : (chunks > most ? most : chunks);
-    eval_metrics_kernel<<<dim3(chunks, H), EM_THREADS, 0, (hipStream_t)stream>>>(a);
+    eval_metrics_kernel<NODES><<<dim3(chunks, H), EM_THREADS, 0, (hipStream_t)stream>>>(a);
     STEP_LAUNCH_CHECK("eval_metrics_accumulate");
     return STEP_OK;
+}
+
+}  // namespace
+
+extern "C" int step_eval_metrics_accumulate(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh,
+                                            long r_sn, int B, int H, int N, float scale, float shift, float null_val, double* acc,
+                                            void* stream) {
+    return eval_metrics_launch<false>("eval_metrics_accumulate", pred, p_sb, p_sh, p_sn, real, r_sb, r_sh, r_sn, B, H, N, scale, shift, null_val,
+                                      acc, stream);
+}
+
+extern "C" int step_eval_metrics_accumulate_nodes(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh,
+                                                  long r_sn, int B, int H, int N, const float* scale_n, const float* shift_n, float null_val,
+                                                  double* acc, void* stream) {
+    return eval_metrics_launch<true>("eval_metrics_accumulate_nodes", pred, p_sb, p_sh, p_sn, real, r_sb, r_sh, r_sn, B, H, N, scale_n, shift_n,
+                                     null_val, acc, stream);
 }
 
 extern "C" int step_eval_metrics_finish(const double* acc, int H, double* out, void* stream) {

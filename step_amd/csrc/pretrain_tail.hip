@@ -9,6 +9,7 @@
 // adjacent) and 48-byte runs of the series.  The work buffer and the device helpers are those of csrc/tail_device.h.
 #include "tail_device.h"
 #include <limits.h>
+#include <cmath>
 
 namespace {
 
@@ -28,6 +29,8 @@ __device__ __forceinline__ f32x4 label4(const PretrainTailArgs& a, unsigned s, u
 }
 
 // Launch 1.  Grid-stride over the S * Pm * 3 vectors of the masked tokens; f32 terms as the reference computes them, summed in f64.
+// NAN_NULL: the mask of a NaN null_val (tail_rescale_null), an instantiation of its own.
+template <bool NAN_NULL>
 __global__ __launch_bounds__(TT_THREADS) void pretrain_tail_reduce_kernel(PretrainTailArgs a) {
 #pragma clang fp contract(off)
     __shared__ double red[TT_WAVES][TT_SUMS];
@@ -40,7 +43,7 @@ __global__ __launch_bounds__(TT_THREADS) void pretrain_tail_reduce_kernel(Pretra
         const unsigned sq = (unsigned)i / m3, rem = (unsigned)i - sq * m3;
         const f32x4 p = load4(a.r, (long)sq * p3 + u3 + rem), y = label4(a, sq, rem);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) tail_accumulate(tail_rescale(p[c], y[c], a.scale, a.shift, a.null_val), s);
+        for (int c = 0; c < 4; ++c) tail_accumulate(tail_rescale_null<NAN_NULL>(p[c], y[c], a.scale, a.shift, a.null_val), s);
     }
     tail_block_add(s, red, a.work, call);
 }
@@ -48,6 +51,7 @@ __global__ __launch_bounds__(TT_THREADS) void pretrain_tail_reduce_kernel(Pretra
 // Launch 2.  Every workgroup reads the finished sums; block 0 writes the loss and the metrics, clears the other half and advances the call
 // index; all of them write dr over the FULL [S, P, 12] as 16-byte vectors (exact zeros in the unmasked rows, at masked labels and at NaN
 // differences).  dr == NULL: one workgroup, values only.
+template <bool NAN_NULL>
 __global__ __launch_bounds__(TT_THREADS) void pretrain_tail_finish_kernel(PretrainTailArgs a, float* __restrict__ loss,
                                                                           float* __restrict__ metrics, float* __restrict__ dr) {
 #pragma clang fp contract(off)
@@ -66,7 +70,7 @@ __global__ __launch_bounds__(TT_THREADS) void pretrain_tail_finish_kernel(Pretra
         if (row3 >= u3) {
             const f32x4 p = load4(a.r, i), y = label4(a, sq, row3 - u3);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) v[c] = tail_sign_grad(tail_rescale(p[c], y[c], a.scale, a.shift, a.null_val), g);
+            for (int c = 0; c < 4; ++c) v[c] = tail_sign_grad(tail_rescale_null<NAN_NULL>(p[c], y[c], a.scale, a.shift, a.null_val), g);
         }
         *reinterpret_cast<f32x4*>(dr + 4 * i) = v;
     }
@@ -81,7 +85,7 @@ extern "C" int step_pretrain_tail(const float* r, const float* series, const int
     STEP_REQUIRE(r && series && mk && work && loss && metrics, "pretrain_tail: NULL buffer");
     STEP_REQUIRE(S > 0 && P > 0 && Pm >= 1 && Pm <= P, "pretrain_tail: need S > 0 and 1 <= Pm <= P (S = %d, P = %d, Pm = %d)", S, P, Pm);
     STEP_REQUIRE((long)S * P * 12 <= INT_MAX, "pretrain_tail: S * P * 12 = %ld exceeds the %d elements of one call", (long)S * P * 12, INT_MAX);
-    STEP_REQUIRE(null_val == null_val, "pretrain_tail: null_val must be finite");
+    STEP_REQUIRE(!std::isinf(null_val), "pretrain_tail: null_val must be finite or NaN");
     STEP_REQUIRE(((uintptr_t)r & 15) == 0 && ((uintptr_t)series & 15) == 0 && ((uintptr_t)dr & 15) == 0,
                  "pretrain_tail: r, series and dr are read and written as 16-byte vectors and must be 16-byte aligned");
     PretrainTailArgs a;
@@ -95,9 +99,16 @@ extern "C" int step_pretrain_tail(const float* r, const float* series, const int
     rblocks = rblocks < 1 ? 1 : (rblocks > 256 ? 256 : rblocks);
     int fblocks = dr ? cdiv(n_all, TT_THREADS) : 1;
     if (fblocks > 2048) fblocks = 2048;
-    pretrain_tail_reduce_kernel<<<rblocks, TT_THREADS, 0, (hipStream_t)stream>>>(a);
-    STEP_LAUNCH_CHECK("pretrain_tail_reduce");
-    pretrain_tail_finish_kernel<<<fblocks, TT_THREADS, 0, (hipStream_t)stream>>>(a, loss, metrics, dr);
+    const hipStream_t st = (hipStream_t)stream;
+    if (null_val != null_val) {
+        pretrain_tail_reduce_kernel<true><<<rblocks, TT_THREADS, 0, st>>>(a);
+        STEP_LAUNCH_CHECK("pretrain_tail_reduce");
+        pretrain_tail_finish_kernel<true><<<fblocks, TT_THREADS, 0, st>>>(a, loss, metrics, dr);
+    } else {
+        pretrain_tail_reduce_kernel<false><<<rblocks, TT_THREADS, 0, st>>>(a);
+        STEP_LAUNCH_CHECK("pretrain_tail_reduce");
+        pretrain_tail_finish_kernel<false><<<fblocks, TT_THREADS, 0, st>>>(a, loss, metrics, dr);
+    }
     STEP_LAUNCH_CHECK("pretrain_tail_finish");
     return STEP_OK;
 }

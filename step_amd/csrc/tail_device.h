@@ -31,6 +31,22 @@ __device__ __forceinline__ TailElem tail_rescale(float p, float y, float scale, 
     return e;
 }
 
+// The tails' own rescale.  NAN_NULL = false is tail_rescale itself; true is the reference's default null_val = NaN (mae.py:17-18): only a
+// NaN label is masked.  A template parameter, not a branch: the loss kernels of csrc/optim.hip call tail_rescale and stay as they are.
+template <bool NAN_NULL>
+__device__ __forceinline__ TailElem tail_rescale_null(float p, float y, float scale, float shift, float null_val) {
+#pragma clang fp contract(off)
+    if constexpr (!NAN_NULL) {
+        return tail_rescale(p, y, scale, shift, null_val);
+    } else {
+        TailElem e;
+        e.p = p * scale + shift;
+        e.y = y * scale + shift;
+        e.m = !isnan(e.y);
+        return e;
+    }
+}
+
 // f32 terms as the reference computes them, added to the lane's f64 sums s[0..4]
 __device__ __forceinline__ void tail_accumulate(const TailElem& e, double* s) {
 #pragma clang fp contract(off)

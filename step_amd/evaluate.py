@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .step_loss import _is_scalar, node_scaler
 
 METRICS = ("MAE", "RMSE", "MAPE")          # the columns of every table below
 MAX_HORIZONS = 64
@@ -62,7 +63,9 @@ def _strides(t, what):
 
 class EvalMetrics:
     """Accumulator of one pass.  ``rescale = (scale, shift)``: the metrics are taken on ``x * scale + shift`` of both tensors (the
-    scaler's std and mean; ``None``: the tensors as they are).  ``null_val`` may be NaN (the reference's default: only NaN labels
+    scaler's std and mean; ``None``: the tensors as they are).  Each of the two may be a scalar or N values (a per-node scaler, as
+    ``step_amd.step_loss.node_scaler`` takes them: element ``(b, h, n)`` is then taken on ``x * scale[n] + shift[n]``; a length other
+    than the tensors' N raises ``ValueError`` in ``update``).  ``null_val`` may be NaN (the reference's default: only NaN labels
     are masked).  Updates of one accumulator must be queued on one stream."""
 
     def __init__(self, horizons=12, null_val=0.0, rescale=None, device=None):
@@ -71,7 +74,12 @@ class EvalMetrics:
         if n <= 0:
             raise ValueError(f"EvalMetrics: horizons = {horizons} is not in 1..{MAX_HORIZONS}")
         self.null_val = float(null_val)
-        self.scale, self.shift = (1.0, 0.0) if rescale is None else (float(rescale[0]), float(rescale[1]))
+        self._nodes = None          # (scale, shift) of a per-node scaler as given; their device copies are node_scaler's
+        if rescale is not None and not (_is_scalar(rescale[0]) and _is_scalar(rescale[1])):
+            self._nodes = (rescale[0], rescale[1])
+            self.scale = self.shift = None
+        else:
+            self.scale, self.shift = (1.0, 0.0) if rescale is None else (float(rescale[0]), float(rescale[1]))
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if dev.type != "cuda":
             raise ValueError("EvalMetrics accumulates on an AMD GPU: libstep_hip has no CPU fallback")
@@ -102,12 +110,16 @@ class EvalMetrics:
             raise ValueError(f"EvalMetrics.update: tensors on {p.device} / {r.device}, accumulator on {self._acc.device}")
         B, H, N = p.shape
         ps, rs = _strides(p, "pred"), _strides(r, "real")          # (checked on the whole tensors: refused before anything is launched)
+        if self._nodes is None:
+            entry, scaler = "step_eval_metrics_accumulate", (self.scale, self.shift)
+        else:
+            scale, shift = node_scaler(self._nodes[1], self._nodes[0], N, self._acc.device, "EvalMetrics.update")
+            entry, scaler = "step_eval_metrics_accumulate_nodes", (_lib.ptr(scale), _lib.ptr(shift))
         g = B if group is None else min(group, B)
         for at in range(0, B, g):
             n = min(g, B - at)
-            _lib.call("step_eval_metrics_accumulate", ctypes.c_void_p(p.data_ptr() + 4 * at * ps[0]), *ps,
-                      ctypes.c_void_p(r.data_ptr() + 4 * at * rs[0]), *rs, n, H, N, self.scale, self.shift, self.null_val,
-                      _lib.ptr(self._acc), _lib.stream())
+            _lib.call(entry, ctypes.c_void_p(p.data_ptr() + 4 * at * ps[0]), *ps, ctypes.c_void_p(r.data_ptr() + 4 * at * rs[0]), *rs,
+                      n, H, N, *scaler, self.null_val, _lib.ptr(self._acc), _lib.stream())
             self.batches += 1
 
     def result(self, horizons=None):
@@ -145,7 +157,8 @@ class EvalMetrics:
 
 def _scale_shift(scaler):
     """(std, mean) of the scaler: ``None``, a ``(mean, std)`` pair, ``{"mean": .., "std": ..}`` or the reference's
-    ``{"func": .., "args": {"mean": .., "std": ..}}`` (``base_tsf_runner.py:238``)"""
+    ``{"func": .., "args": {"mean": .., "std": ..}}`` (``base_tsf_runner.py:238``).  Scalars come back as floats; N values (numpy
+    arrays or tensors, the per-node scaler of ``--norm_each_channel``) as they are, for ``EvalMetrics`` to check against the data"""
     if scaler is None:
         return None
     if isinstance(scaler, dict):
@@ -153,6 +166,8 @@ def _scale_shift(scaler):
         mean, std = args["mean"], args["std"]
     else:
         mean, std = scaler
+    if not (_is_scalar(mean) and _is_scalar(std)):
+        return std, mean          # (node_scaler checks length and finiteness where N is known: in front of the first update's launch)
     mean, std = float(mean), float(std)
     if not (math.isfinite(mean) and math.isfinite(std)):
         raise ValueError(f"STEP.evaluate: scaler mean = {mean}, std = {std} must be finite")

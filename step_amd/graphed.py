@@ -20,7 +20,9 @@ Usage (a runner's ``train_iters`` replacement)::
         loss = step(hist, long_hist, fut)        # device scalar of THIS step, valid until the next call
 
 Restrictions: fixed batch shape; single process (the gradient collectives of ``enable_native_data_parallel`` are not captured);
-``FusedAdamClip`` as the optimizer; the warm-up iterations before the capture are real optimizer steps on the example batch.
+``FusedAdamClip`` as the optimizer; the warm-up iterations before the capture are real optimizer steps on the example batch; a finite
+``null_val`` and a scalar ``scaler`` (the NaN mask and per-node scalers of ``step_loss.train_tail`` are not captured: its loss kernels
+read the device-resident coefficient, ``train_tail`` does not).
 """
 import ctypes
 import os

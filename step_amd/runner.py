@@ -378,14 +378,16 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
     ``native_tail``: take the loss, its gradients and the three training meters of an iteration from ONE ``step_loss.train_tail`` call
     on the model's normalised prediction and the batch's target view -- no rescale, no ``[:, :cl_length]`` slice, no copy -- also under
     curriculum learning (``CFG.TRAIN.CL``).  Needs a ``STEP`` module on a GPU, the ``re_standard_transform`` scaler with scalar
-    mean / std, ``step_loss`` / ``step_loss_native`` as the loss, only the three basicts metrics and a finite ``null_val``; anything
-    else takes the base class's path as with ``native_tail=False`` (the default).
+    mean / std or with the per-node arrays of ``--norm_each_channel`` (``np.ndarray`` of shape ``(1, N, 1)`` or ``(N, 1)``, N the
+    prediction's), ``step_loss`` / ``step_loss_native`` as the loss, only the three basicts metrics and a real ``null_val`` that is not
+    infinite (NaN, the reference's default, masks nothing but missing labels); anything else takes the base class's path as with
+    ``native_tail=False`` (the default).
     ``native_pretrain``: for ``TSFormerRunner`` (``step/TSFormer_*.py``) around a ``TSFormer`` in pre-train mode on a GPU, not wrapped:
     ``init_training`` flattens the module's parameters and swaps ``torch.optim.Adam`` + ``clip_grad_norm_`` for ``FusedAdamClip`` (under
     the conditions of the STEP branch), and ``train_iters`` / ``val_iters`` take the loss, its gradient and the three meters from ONE
     ``TSFormer.pretrain_tail`` call (validation under ``no_grad``, nothing read back).  That needs the ``re_standard_transform`` scaler
-    with scalar mean / std, ``masked_mae`` (basicts' or this package's) as the loss, only the three basicts metrics, a finite
-    ``null_val`` and no ``CFG.TRAIN.CL``; anything else takes the base class's path as with ``native_pretrain=False`` (the default).
+    with scalar mean / std (a per-node scaler stays on the base path here), ``masked_mae`` (basicts' or this package's) as the loss,
+    only the three basicts metrics, a real ``null_val`` that is not infinite (NaN included) and no ``CFG.TRAIN.CL``; anything else takes the base class's path as with ``native_pretrain=False`` (the default).
     ``native_data_parallel``: for a launch on several GPUs (``CFG.GPU_NUM = 2`` in fifteen of the reference's sixteen ``step/*.py``
     configs), where easytorch wraps the model in ``DistributedDataParallel``.  ``init_training`` -- after easytorch has built Adam and
     the scheduler and resumed a checkpoint -- takes the module out of the wrap and calls its ``enable_native_data_parallel()`` (rank 0's
@@ -413,8 +415,8 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
     ``native_eval``: the validation meters of the forecasting stage come from one ``step_amd.EvalMetrics`` per pass -- ``val_iters``
     queues ONE accumulate launch on the model's normalised prediction and the batch's target view (no rescale, no metric functions, no
     ``.item()``), and ``flush_meters`` reads the mean of the per-batch values back once per pass, before ``save_best_model`` looks at
-    ``val_MAE``.  Needs a ``STEP`` module on a GPU, the ``re_standard_transform`` scaler with scalar mean / std, only the three basicts
-    metrics and a real ``null_val`` (NaN included); anything else takes the base class's ``val_iters`` as with ``native_eval=False``
+    ``val_MAE``.  Needs a ``STEP`` module on a GPU, the ``re_standard_transform`` scaler with scalar mean / std or per-node arrays (as for
+    ``native_tail``), only the three basicts metrics and a real ``null_val`` (NaN included); anything else takes the base class's ``val_iters`` as with ``native_eval=False``
     (the default).  Under ``native_pretrain`` the runner's ``test()`` (``TSFormerRunner.test``) likewise takes the three ``test_``
     meters of a batch from one ``pretrain_tail`` call and reads nothing back before the meters are printed.
     ``eval_batch_size``: ``E`` windows per validation / test forward instead of the config's ``VAL/TEST.DATA.BATCH_SIZE``: the look-ahead
@@ -445,7 +447,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
     rescaled and sliced per horizon) feeds every batch to one ``step_amd.EvalMetrics`` instead -- one launch per batch, nothing
     concatenated, ONE read-back -- logs the reference's line for each of ``self.evaluation_horizons`` and sets ``test_MAE`` /
     ``test_RMSE`` / ``test_MAPE`` from the table's overall row.  Under the conditions of ``native_eval`` (a ``STEP`` on a GPU, the
-    ``re_standard_transform`` scaler with scalar mean / std, only the three basicts metrics, a real ``null_val``); anything else takes
+    ``re_standard_transform`` scaler with scalar mean / std or per-node arrays, only the three basicts metrics, a real ``null_val``); anything else takes
     the base class's ``test()``.  The pre-training branch of ``test()`` is not affected.
     ``spread_eval``: where ``native_data_parallel`` acts on a ``STEP``, the validation and the test pass of an epoch's end are spread
     over the ranks instead of running on rank 0 while the others wait: batch ``c`` of a pass is evaluated by rank ``c % world``
@@ -814,7 +816,11 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             return self._scalar_rescale(("step_loss", "step_loss_native"))
 
         def _scaler_mean_std(self):
-            """(mean, std) of a ``re_standard_transform`` scaler with scalar real arguments, else None"""
+            """(mean, std) of a ``re_standard_transform`` scaler: floats for scalar real arguments; the arrays themselves for two
+            ``np.ndarray`` of one shape ``(1, N, 1)`` or ``(N, 1)`` -- what ``standard_transform`` pickles under ``--norm_each_channel``
+            and ``re_standard_transform`` (basicts/data/transform.py:59-65) broadcasts per node against ``[B, H, N, 1]``.  Anything else
+            is None (the base path): torch tensors, a scalar next to an array (the reference fails on it), and shape ``(N,)``, which the
+            reference broadcasts against the LAST dimension"""
             scaler = getattr(self, "scaler", None)
             if not isinstance(scaler, dict):
                 return None
@@ -822,22 +828,43 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             if getattr(func, "__name__", func) != "re_standard_transform":
                 return None
             mean, std = args.get("mean"), args.get("std")
+            if isinstance(mean, np.ndarray) and isinstance(std, np.ndarray):
+                per_node = mean.shape == std.shape and (mean.ndim == 2 or (mean.ndim == 3 and mean.shape[0] == 1)) and mean.shape[-1] == 1
+                if not (per_node and mean.size > 0 and all(x.dtype.kind == "f" and np.isfinite(x).all() for x in (mean, std))):
+                    return None
+                return mean, std
             if isinstance(mean, bool) or isinstance(std, bool) or not (isinstance(mean, numbers.Real) and isinstance(std, numbers.Real)):
                 return None
             return float(mean), float(std)
+
+        @staticmethod
+        def _scaler_fits(scaler, pred):
+            """a per-node scaler has as many nodes as the forward's ``[B, H, N, 1]`` prediction (scalars fit anything)"""
+            mean = scaler[0]
+            return not isinstance(mean, np.ndarray) or (torch.is_tensor(pred) and pred.dim() == 4 and mean.size == pred.shape[2])
+
+        @staticmethod
+        def _rescaled(x, mean, std):
+            """``re_standard_transform`` on torch ops (basicts/data/transform.py:59-65), for the tails that run after a forward whose
+            outputs the native calls cannot take"""
+            if isinstance(mean, np.ndarray):
+                mean = torch.from_numpy(mean).type_as(x).to(x.device).unsqueeze(0)
+                std = torch.from_numpy(std).type_as(x).to(x.device).unsqueeze(0)
+            return x * std + mean
 
         def _only_basicts_metrics(self):
             metrics = getattr(self, "metrics", None)
             return isinstance(metrics, dict) and all(self._is_basicts_metric(f) for f in metrics.values())
 
         def _scalar_rescale(self, loss_names):
-            """(mean, std) of a ``re_standard_transform`` scaler with scalar arguments when the loss is one of ``loss_names``, the metrics
-            are the three of basicts and ``null_val`` is finite, else None"""
+            """(mean, std) of ``_scaler_mean_std`` (scalars, or per-node arrays) when the loss is one of ``loss_names``, the metrics are
+            the three of basicts and ``null_val`` is a real number that is not infinite (NaN, the reference's default, is allowed; a
+            ``bool`` is not), else None"""
             scaler = self._scaler_mean_std()
             if scaler is None or getattr(self.loss, "__name__", None) not in loss_names or not self._only_basicts_metrics():
                 return None
             nv = getattr(self, "null_val", 0.0)
-            if not (isinstance(nv, numbers.Real) and math.isfinite(nv)):
+            if isinstance(nv, bool) or not isinstance(nv, numbers.Real) or math.isinf(nv):
                 return None
             return scaler
 
@@ -860,7 +887,10 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
 
         def _val_accumulator(self, horizons, mean, std, device):
             """the pass's ``EvalMetrics``: made on first use, kept over the epochs, made anew when what it was built for changes"""
-            key = (int(horizons), repr(float(self.null_val)), std, mean, device)
+            # (arrays do not compare as keys do: a per-node scaler is told apart by the arrays' identity and shape -- the runner holds
+            # them for its lifetime -- a scalar one by its values)
+            ident = tuple((id(x), x.shape) if isinstance(x, np.ndarray) else x for x in (std, mean))
+            key = (int(horizons), repr(float(self.null_val)), ident, device)
             if self._val_metrics is None or self._val_metrics[0] != key:
                 self._drain_val_metrics()          # (nothing to drain unless the key changed in the middle of a pass)
                 from .evaluate import EvalMetrics
@@ -895,14 +925,14 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             mean, std = scaler
             forward_return = self.forward(data=data, epoch=None, iter_num=None, train=False)
             pred, real = forward_return[0], forward_return[1]
-            ok = self._qualifies(pred, real)
+            ok = self._qualifies(pred, real) and self._scaler_fits(scaler, pred)
             if not ok and self._spread_acting:
                 raise RuntimeError("step_amd.runner: a validation forward whose outputs EvalMetrics cannot take, in a pass spread over the "
                                    "ranks (spread_eval): the torch path would leave the other ranks waiting in the pass's collective")
             if not ok:
                 # the forward pass is done and cannot be repeated: the base class's tail (:267-273) on torch ops, the scaler being
-                # re_standard_transform with scalar mean / std (basicts/data/transform.py:59-65)
-                prediction_rescaled, real_value_rescaled = pred * std + mean, real * std + mean
+                # re_standard_transform (basicts/data/transform.py:59-65)
+                prediction_rescaled, real_value_rescaled = self._rescaled(pred, mean, std), self._rescaled(real, mean, std)
                 for metric_name, metric_func in self.metrics.items():
                     metric_item = self.metric_forward(metric_func, [prediction_rescaled, real_value_rescaled])
                     self.update_epoch_meter("val_" + metric_name, metric_item.item())
@@ -920,12 +950,15 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                 return None
             if not str(getattr(self.loss, "__module__", "")).startswith(("basicts.", "step_amd.")):
                 return None
-            return self._scalar_rescale(("masked_mae", "masked_mae_native"))
+            scaler = self._scalar_rescale(("masked_mae", "masked_mae_native"))
+            # (a per-node scaler: the reference's broadcast against the pre-training [B, L', N] does not mean "per node" -- the base path)
+            return None if scaler is None or isinstance(scaler[0], np.ndarray) else scaler
 
         def _pretrain_tail(self, data, scaler):
             """tsformer_runner.py:57-65 and base_tsf_runner.py:240-254 (:266-273 in validation) from one pretrain_tail call"""
             history_data = self.select_input_features(self.to_running_device(data[1]))
-            return self.model.pretrain_tail(history_data, null_val=float(self.null_val), rescale=scaler)
+            nv = float(self.null_val)
+            return self.model.pretrain_tail(history_data, null_val=None if nv != nv else nv, rescale=scaler)          # (None: the NaN rule)
 
         def val_iters(self, iter_index, data):
             scaler = self._pretrain_scaler(data) if native_pretrain else None
@@ -981,7 +1014,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                 for data in loader:
                     forward_return = self.forward(data, epoch=None, iter_num=None, train=False)
                     pred, real = forward_return[0], forward_return[1]
-                    if not self._qualifies(pred, real):
+                    if not (self._qualifies(pred, real) and self._scaler_fits(scaler, pred)):
                         if m is None and base_test is not None and not self._spread_acting:
                             return base_test()
                         raise RuntimeError("step_amd.runner: native_test met a forward whose outputs EvalMetrics cannot take "
@@ -1049,12 +1082,13 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                 ok = (torch.is_tensor(pred) and torch.is_tensor(real) and pred.is_cuda and real.is_cuda and pred.dtype == torch.float32
                       and real.dtype == torch.float32 and pred.dim() == 4 and pred.shape[3] == 1 and pred.shape == real.shape
                       and pred.shape[1] <= 64 and torch.is_tensor(theta) and theta.is_cuda and theta.dtype == torch.float32
-                      and torch.is_tensor(prior) and not torch.is_tensor(coef) and (cl is None or 1 <= cl <= pred.shape[1]))
+                      and torch.is_tensor(prior) and not torch.is_tensor(coef) and (cl is None or 1 <= cl <= pred.shape[1])
+                      and self._scaler_fits(scaler, pred))
             if not ok:
                 # the forward pass is done and cannot be repeated: the base class's tail (:240-254) on torch ops, the scaler being
-                # re_standard_transform with scalar mean / std (basicts/data/transform.py:59-65)
-                forward_return[0] = forward_return[0] * std + mean
-                forward_return[1] = forward_return[1] * std + mean
+                # re_standard_transform (basicts/data/transform.py:59-65)
+                forward_return[0] = self._rescaled(forward_return[0], mean, std)
+                forward_return[1] = self._rescaled(forward_return[1], mean, std)
                 if cl is not None:
                     forward_return[0] = forward_return[0][:, :cl, :, :]
                     forward_return[1] = forward_return[1][:, :cl, :, :]

@@ -1014,16 +1014,20 @@ class TSFormer(nn.Module):
         parameters: its gradient reaches the native backward in the layout of the decoder's output, without the slice, gather, transpose
         and zero-fill launches of the views ``forward()`` returns.  ``metrics`` is an f32 ``[3]`` tensor (masked MAE, RMSE, MAPE of
         basicts/metrics on the same elements), no gradient.  ``history_data``: what ``forward()`` takes in pre-train mode, a device
-        tensor ``[B, L, N, C]`` or a ``LongHistoryRef``.  ``null_val`` must be finite.  Under ``torch.no_grad()`` only the values are
-        computed."""
+        tensor ``[B, L, N, C]`` or a ``LongHistoryRef``.  ``null_val``: a finite number, or None for "no null value": only missing
+        (NaN) labels are masked, the reference's default ``null_val = nan`` (mae.py:17-18).  A float NaN or infinity raises
+        ``ValueError`` as it always did here; ``native_runner`` hands a configured NaN over as None.  ``rescale`` takes scalars only:
+        the reference's broadcast of a per-node scaler against ``[B, L', N]`` does not mean "per node".  Under ``torch.no_grad()`` only
+        the values are computed."""
         if self.mode != "pre-train":
             raise ValueError("TSFormer.pretrain_tail: the module is not in pre-train mode")
         from .step import LongHistoryRef
+        nan_null = null_val is None
         if not (isinstance(history_data, LongHistoryRef) or (torch.is_tensor(history_data) and history_data.dim() == 4)):
             raise ValueError("TSFormer.pretrain_tail: history_data must be a [B, L, N, C] device tensor or a LongHistoryRef")
-        null_val = float(null_val)
-        if null_val != null_val or null_val in (float("inf"), float("-inf")):
-            raise ValueError("TSFormer.pretrain_tail: null_val must be finite")
+        null_val = float("nan") if null_val is None else float(null_val)
+        if null_val in (float("inf"), float("-inf")) or (null_val != null_val and not nan_null):
+            raise ValueError("TSFormer.pretrain_tail: null_val must be finite (None: only NaN labels are masked)")
         if not history_data.is_cuda:
             raise RuntimeError("step_amd.TSFormer runs only on an AMD GPU (no CPU fallback)")
         mean, std = (0.0, 1.0) if rescale is None else (float(rescale[0]), float(rescale[1]))

@@ -12,8 +12,19 @@ alternate inside one loop; the device is idle before every timed tail).  There i
 and no copies".
 
     python tools/bench_train_tail.py [--out profiles/train_tail.json]
+
+``--null nan`` and / or ``--scaler node`` (and ``--parent-lib``) switch to another measurement, of the tail's own two launches under the
+variants this tool did not have: the entry points of libstep_hip called directly (``step_train_tail`` / ``step_train_tail_nodes``) on the
+same tensors at C2's shape (B = 8, H = 12, N = 307) and at N = 883, k = 12 -- the scalar / finite tail, the NaN ``null_val`` tail
+(``--null nan``), the per-node tail (``--scaler node``) and, with ``--parent-lib PATH``, the scalar / finite tail of ANOTHER build of
+libstep_hip (the parent commit's) loaded next to this tree's.  Device microseconds between two events around the two launches, medians
+of --iters with the p10-p90 band, the variants alternating inside one loop.  No threshold for the new variants; what to read off is
+whether the scalar / finite medians of the two builds lie within each other's band (``default_within_bands``).
+
+    python tools/bench_train_tail.py --null nan --scaler node --parent-lib PATH [--out profiles/tail_scalers.json] [--merge]
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -71,14 +82,103 @@ def launches(fn, args, n=10):
     return sum(names.values()) / n, {k: v / n for k, v in sorted(names.items())}
 
 
+def _band(xs):
+    q = statistics.quantiles(xs, n=10)
+    return {"device_us": statistics.median(xs), "device_us_p10_p90": [q[0], q[-1]]}
+
+
+def variants_main(a):
+    """the tail's two launches under (null_val, scaler) variants, and under another build of the library: see the module docstring"""
+    from step_amd import _lib
+    lib = _lib.lib()
+    libs = {"tree": lib}
+    if a.parent_lib:
+        parent = ctypes.CDLL(os.path.abspath(a.parent_lib))
+        for name in ("step_train_tail", "step_train_tail_work_doubles"):
+            getattr(parent, name).restype, getattr(parent, name).argtypes = _lib._SIGS[name]
+        libs["parent"] = parent
+    gen = torch.Generator().manual_seed(0)
+    nan = float("nan")
+    rows = []
+    for label, (B, N) in (("C2 STEP_PEMS04", SHAPES["C2 STEP_PEMS04"]), ("N=883 B=8", (8, 883))):
+        pred, fut, theta, prior = inputs(B, N, gen)
+        pred = pred[..., 0].contiguous()
+        scale_n, shift_n = torch.full((N,), STD).cuda(), torch.full((N,), MEAN).cuda()
+        scale_n *= torch.linspace(0.8, 1.25, N).cuda()
+        loss, metrics = torch.empty((), device="cuda"), torch.empty(3, device="cuda")
+        dp, dt = torch.empty_like(pred), torch.empty_like(theta)
+        work = {k: torch.zeros(lb.step_train_tail_work_doubles(), dtype=torch.float64, device="cuda") for k, lb in libs.items()}
+
+        def call(which, entry, scaler, null_val):
+            rc = getattr(libs[which], entry)(_lib.ptr(pred), H * N, N, 1, ctypes.c_void_p(fut.data_ptr()), H * N * C, N * C, C, B, H, N, H, *scaler,
+                                             null_val, _lib.ptr(theta), _lib.ptr(prior), theta.numel(), 0.5, _lib.ptr(work[which]), _lib.ptr(loss),
+                                             _lib.ptr(metrics), _lib.ptr(dp), _lib.ptr(dt), _lib.stream())
+            assert rc == 0, (which, entry, rc)
+
+        variants = [("scalar_finite", ("tree", "step_train_tail", (STD, MEAN), 0.0))]
+        if a.null == "nan":
+            variants.append(("nan_null", ("tree", "step_train_tail", (STD, MEAN), nan)))
+        if a.scaler == "node":
+            variants.append(("per_node", ("tree", "step_train_tail_nodes", (_lib.ptr(scale_n), _lib.ptr(shift_n)), 0.0)))
+            if a.null == "nan":
+                variants.append(("per_node_nan_null", ("tree", "step_train_tail_nodes", (_lib.ptr(scale_n), _lib.ptr(shift_n)), nan)))
+        if a.parent_lib:
+            variants.append(("parent_scalar_finite", ("parent", "step_train_tail", (STD, MEAN), 0.0)))
+        dev = {name: [] for name, _ in variants}
+        values = {}
+        for it in range(a.warmup + a.iters):
+            for name, args in variants:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                call(*args)
+                e1.record()
+                e1.synchronize()
+                if it >= a.warmup:
+                    dev[name].append(1e3 * e0.elapsed_time(e1))
+                if it == 0:
+                    values[name] = (float(loss), metrics.tolist(), dp.clone())
+        row = {"shape": label, "B": B, "N": N, "k": H, **{name: dict(_band(dev[name]), loss=values[name][0]) for name, _ in variants}}
+        if a.parent_lib:
+            t, p = row["scalar_finite"], row["parent_scalar_finite"]
+            row["default_within_bands"] = bool(p["device_us_p10_p90"][0] <= t["device_us"] <= p["device_us_p10_p90"][1]
+                                               and t["device_us_p10_p90"][0] <= p["device_us"] <= t["device_us_p10_p90"][1])
+            row["default_same_bits_as_parent"] = bool(values["scalar_finite"][0] == values["parent_scalar_finite"][0]
+                                                      and values["scalar_finite"][1] == values["parent_scalar_finite"][1]
+                                                      and torch.equal(values["scalar_finite"][2], values["parent_scalar_finite"][2]))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    out = {}
+    if a.merge and os.path.exists(a.out):
+        with open(a.out) as f:
+            out = json.load(f)
+    out.update({"tool": "tools/bench_train_tail.py --null nan --scaler node --parent-lib ...", "device": torch.cuda.get_device_name(0),
+                "iters": a.iters, "warmup": a.warmup,
+                "what": "the training tail's two launches (libstep_hip entry points called directly, k = 12): device microseconds between "
+                        "two events, medians and p10-p90, the variants alternating inside one loop; parent_scalar_finite is the parent "
+                        "commit's build of the library loaded next to this tree's", "tail_rows": rows})
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    print("wrote", a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_tail.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--null", choices=("zero", "nan"), default="zero", help="nan: also time the tail under a NaN null_val")
+    ap.add_argument("--scaler", choices=("scalar", "node"), default="scalar", help="node: also time the per-node tail")
+    ap.add_argument("--parent-lib", default=None, metavar="PATH", help="another build of libstep_hip.so whose scalar / finite tail is timed in the same loop")
+    ap.add_argument("--merge", action="store_true", help="keep the other keys of an existing --out file")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_train_tail: needs a GPU (nothing is measured without one)")
+    if a.null == "nan" or a.scaler == "node" or a.parent_lib:
+        a.out = a.out or os.path.join(ROOT, "profiles", "tail_scalers.json")
+        return variants_main(a)
+    a.out = a.out or os.path.join(ROOT, "profiles", "train_tail.json")
     gen = torch.Generator().manual_seed(0)
     paths = (("existing", tail_existing), ("train_tail", tail_native))
     rows = []
