@@ -769,6 +769,14 @@ static bool dgl_channels_last(const StepDglParams* p) {
     return p->gemm_bf16 && !(e && e[0] == '1');
 }
 
+// The two fc products over a2h of the channels-last path run on the streaming kernels of dgl_fc_stream.hip; STEP_DGL_FC_STREAM=0 keeps
+// the staged GEMM for both (A/B measurements).  Read on every call; the two paths share every buffer layout, so forward and backward
+// may differ.
+static bool dgl_fc_stream() {
+    const char* e = getenv("STEP_DGL_FC_STREAM");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+
 // STEP_DGL_LEGACY_BN=1 in the environment keeps the three-pass BatchNorm backward (A/B measurements, debugging)
 static bool dgl_legacy_bn_backward() {
     const char* e = getenv("STEP_DGL_LEGACY_BN");
@@ -904,7 +912,8 @@ static int dgl_global_forward_impl(const float* series_nt, int N, int T, const S
             gm.splitk_ws = (float*)(((uintptr_t)ws + 15) & ~(uintptr_t)15);
             gm.splitk_ws_floats = fc_splitk_ws_floats(N, T2) - 4;
         }
-        STEP_TRY(step_gemm_launch(gm, st));
+        if (cl && dgl_fc_stream()) STEP_TRY(dgl_fc_stream_fwd(a2, wp, N, EMB, K, gpre, gm.splitk_ws, gm.splitk_ws_floats, st));
+        else STEP_TRY(step_gemm_launch(gm, st));
     }
     if (all || phase == 4) {
         fc_post_bn3_kernel<<<EMB, 256, 0, st>>>(gpre, p->fc_b, N, p->bn3_w, p->bn3_b, p->bn3_rm, p->bn3_rv, training, momentum, st3, g);
@@ -1011,7 +1020,9 @@ static int dgl_global_backward_impl(const float* series_nt, int N, int T, const 
             StepGemm gm = gemm_desc(EMB, (int)K, N, dgpre, 1, EMB, a2, K, 1, wraw, K);
             gm.b_bf16 = 1;
             gm.compute_bf16 = 1;
-            STEP_TRY(step_gemm_launch(gm, st));
+            // (the streaming kernel keeps all nodes of dgpre^T resident: graphs beyond its 320 rows stay on the staged GEMM)
+            if (dgl_fc_stream() && dgl_fc_stream_wgrad_ok(N)) STEP_TRY(dgl_fc_stream_wgrad(a2, dgpreT, N, EMB, K, wraw, st));
+            else STEP_TRY(step_gemm_launch(gm, st));
             if (hipMemsetAsync(dots_o, 0, EMB * 32 * sizeof(float), st) != hipSuccess) { step_set_error("memset failed"); return STEP_ERR_HIP; }
             fc_unpermute_kernel<<<dim3(cdiv(T2, 256), EMB), 256, 0, st>>>(wraw, p->fc_w, st2, colsum, grads->fc_w, dots_o, T2, fresh_fc);
             dots_reduce_kernel<<<1, 64, 0, st>>>(dots_o, dots);

@@ -7,6 +7,7 @@
 // torch.topk cuts ties arbitrarily, so parity is "identical except at ties on the threshold".
 #include "common.h"
 #include "step_internal.h"
+#include "lds_dma.h"
 
 namespace {
 
@@ -221,16 +222,7 @@ __device__ __forceinline__ void gs_block_of(int p, int NB, int& bi, int& bj) {
     while (p >= NB - bi) { p -= NB - bi; ++bi; }
     bj = bi + p;
 }
-// lane i's 16 bytes land at lds_dst + 16 i (lds_dst wave-uniform): global_load_lds_dwordx4, no registers in between
-__device__ __forceinline__ void gs_dma_1k(const void* gsrc_lane, uint32_t lds_dst) {
-    uint32_t keep;
-    lds_dst = __builtin_amdgcn_readfirstlane(lds_dst);
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc_lane), "s"(lds_dst)
-                 : "memory");
-}
-// Staging: a slab of all 64 NB (padded) rows goes from global memory straight into one of three LDS buffers by DMA -- NB instructions of 1 KB
+// Staging (lds_dma_1k, lds_dma.h: lane i's 16 bytes land at lds_dst + 16 i): a slab of all 64 NB (padded) rows goes from global memory straight into one of three LDS buffers by DMA -- NB instructions of 1 KB
 // (8 rows) from each of waves 0..7, two slabs ahead of the matrix work.  A row's 8 pieces are stored XOR-swizzled (piece c of row r in slot
 // c ^ (r & 7): the DMA fixes where a lane's data lands, not what it loads), so the 16-byte fragment reads of 8 consecutive rows hit all 32
 // banks.  Rows beyond N repeat row N - 1: they only feed outputs that are never stored.  LDS moves 1 KB per matrix product here (four
@@ -264,7 +256,7 @@ __global__ __launch_bounds__(1024) void gram_sym_kernel(const uint16_t* __restri
                 int row = g * 8 + (lane >> 3);
                 const int c = (lane & 7) ^ (row & 7);
                 row = row < N ? row : N - 1;
-                gs_dma_1k(Hb + (long)row * F + k0 + c * 8, lds0 + (uint32_t)(buf * BUF + g * 1024));
+                lds_dma_1k(Hb + (long)row * F + k0 + c * 8, lds0 + (uint32_t)(buf * BUF + g * 1024));
             }
         }
     };

@@ -78,6 +78,10 @@ long dgl_conv2_wgrad_scratch_floats(int N, int T1);
 int dgl_conv2_wgrad_mfma(const float* dz, const float* a1, const float* sc, const float* sh, float* scratch, float* dw, float* db, int N,
                          int T1, hipStream_t st);
 int dgl_conv1_wgrad_mfma(const float* dz, const float* x, float* scratch, float* dw, float* db, int N, int T, hipStream_t st);
+// streaming fc products of the channels-last path (dgl_fc_stream.hip)
+int dgl_fc_stream_fwd(const void* a2h, const void* wp, int N, int O, long K, float* gpre, float* ws, long ws_floats, hipStream_t st);
+bool dgl_fc_stream_wgrad_ok(int N);
+int dgl_fc_stream_wgrad(const void* a2h, const float* dgpreT, int N, int O, long K, float* G, hipStream_t st);
 int step_colsum_launch(const float* x, long rows, int cols, long ld, float* out, hipStream_t st);
 
 // Fork / join of leaf work onto a second stream (events from a per-thread, per-device pool): the data-gradient chain of a backward
