@@ -207,6 +207,23 @@ int step_dgl_global_backward_shard(const float* series_slice, int N, int Ts, con
                                    void* stream);
 long step_dgl_global_offset(int N, int T, int item);
 
+/* The fc input gradient of the global feature's backward on caller-owned buffers (additive to ABI 10): the gradient of
+ * discrete_graph_learning.py:131-136 with respect to conv2's pre-activation in the channels-last bf16 layout of p->gemm_bf16 = 1 --
+ * back through fc, BatchNorm2 (batch statistics) and conv2's ReLU in one launch.  For n < N, k < K (K = 16 (T - 18), a multiple of 16),
+ * c = k mod 16:
+ *     v   = sum_o bf16(dgpre[n][o]) * wp[o][k]          (o = 0 .. 99; bf16 products on the matrix cores, f32 accumulation, o ascending)
+ *     x   = a2h[n][k]
+ *     km1 = coef[32+c] * coef[c];  km2 = coef[32+c] * coef[16+c] * st2[48+c];  mu = st2[32+c]           (f32)
+ *     dz2h[n][k] = bf16( x > 0 ? v - km1 - (x - mu) * km2 : 0 )           (round to nearest even; a2h = +-0 is a closed ReLU)
+ *  dgpre f32 [N][100]; wp bf16 [100][K] (the forward's BatchNorm2-scaled, (t, c)-ordered fc weight); a2h bf16 [N][K]; coef f32 [48]
+ *  (BatchNorm2's backward means m1 [16], m2 [16] and its scale [16]); st2 f32 [64] (forward statistics: [32,48) mean, [48,64) rstd);
+ *  dz2h bf16 [N][K], nothing outside it is written.  dgpre, wp, a2h, dz2h 16-byte aligned.  Runs what the backward runs: the streaming
+ *  kernel, or with STEP_DGL_FC_STREAM=0 in the environment the staged GEMM; both store the same bits. */
+int step_dgl_fc_dgrad(const float* dgpre, const void* wp, const void* a2h, const float* coef, const float* st2, int N, long K,
+                      void* dz2h, void* stream);
+/* 1: that size runs on the streaming kernel under the current environment, 0: on the staged GEMM (a pure host function). */
+long step_dgl_fc_dgrad_streams(int N, long K);
+
 /* Edge logits + Gumbel-softmax hard sample (discrete_graph_learning.py:148-161, :11-45).
  *  g [N,100]; u f32 [B, N*N, 2] uniform noise as drawn by torch.rand (:12) or NULL for the
  *  on-device Philox stream keyed by seed.  Outputs theta[B,N,N] = softmax(logits)[...,0]

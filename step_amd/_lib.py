@@ -81,6 +81,8 @@ _SIGS = {
     "step_dgl_global_forward_shard": (_i, [_vp, _i, _i, _PD, _i, _f, _vp, _vp, _vp, _vp, _PS, _i, _vp]),
     "step_dgl_global_backward_shard": (_i, [_vp, _i, _i, _PD, _vp, _vp, _vp, _PD, _PS, _i, _vp]),
     "step_dgl_global_offset": (_l, [_i, _i, _i]),
+    "step_dgl_fc_dgrad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _l, _vp, _vp]),
+    "step_dgl_fc_dgrad_streams": (_l, [_i, _l]),
     "step_dgl_edges_saved_floats": (_l, [_i, _i]),
     "step_dgl_edges_work_floats": (_l, [_i]),
     "step_dgl_edges_theta_offset": (_l, [_i]),

@@ -769,12 +769,35 @@ static bool dgl_channels_last(const StepDglParams* p) {
     return p->gemm_bf16 && !(e && e[0] == '1');
 }
 
-// The two fc products over a2h of the channels-last path run on the streaming kernels of dgl_fc_stream.hip; STEP_DGL_FC_STREAM=0 keeps
-// the staged GEMM for both (A/B measurements).  Read on every call; the two paths share every buffer layout, so forward and backward
+// The three fc products over a2h of the channels-last path run on the streaming kernels of dgl_fc_stream.hip; STEP_DGL_FC_STREAM=0 keeps
+// the staged GEMM for all of them (A/B measurements).  Read on every call; the two paths share every buffer layout, so forward and backward
 // may differ.
 static bool dgl_fc_stream() {
     const char* e = getenv("STEP_DGL_FC_STREAM");
     return !(e && e[0] == '0' && e[1] == 0);
+}
+
+// dz2h = BatchNorm2 backward of dgpre @ fc_w, masked by conv2's ReLU, channels-last bf16 rows [N][K = 16 (T - 18)]: the scale rides in wp
+// (the forward's scaled (t, c)-ordered bf16 weight), the rest in the epilogue.  One pass over a2h / dz2h on the streaming kernel, or
+// (STEP_DGL_FC_STREAM=0, sizes outside dgl_fc_stream_dgrad_ok) the staged GEMM with its fused epilogue; the two store the same bits.
+// (Round 4's register-resident column strips, profiles/r04_l_fc_dgrad_strips_ab.log, had no DMA ring and were no faster than the GEMM.)
+static int dgl_fc_dgrad(const float* dgpre, const void* wp, const void* a2h, const float* coef, const float* st2, int N, long K, void* dz2h,
+                        hipStream_t st) {
+    if (dgl_fc_stream() && dgl_fc_stream_dgrad_ok(N, K)) return dgl_fc_stream_dgrad(dgpre, wp, a2h, coef, st2, N, EMB, K, dz2h, st);
+    StepGemm gm = gemm_desc(N, (int)K, EMB, dgpre, EMB, 1, (const float*)wp, K, 1, (float*)dz2h, K);
+    gm.b_bf16 = 1;
+    gm.compute_bf16 = 1;
+    GemmFused fu = {nullptr, nullptr, (const float*)a2h, coef, st2, 16, (int)(K / 16), GEMM_FUSED_INTERLEAVED};
+    return step_gemm_launch_fused(gm, fu, st);
+}
+
+extern "C" long step_dgl_fc_dgrad_streams(int N, long K) { return dgl_fc_stream() && dgl_fc_stream_dgrad_ok(N, K) ? 1 : 0; }
+
+extern "C" int step_dgl_fc_dgrad(const float* dgpre, const void* wp, const void* a2h, const float* coef, const float* st2, int N, long K,
+                                 void* dz2h, void* stream) {
+    STEP_REQUIRE(dgpre && wp && a2h && coef && st2 && dz2h && N > 0 && K > 0 && K % 16 == 0 && K <= 0x7fffffffL, "dgl_fc_dgrad: bad arguments");
+    STEP_REQUIRE(((((uintptr_t)dgpre) | ((uintptr_t)wp) | ((uintptr_t)a2h) | ((uintptr_t)dz2h)) & 15) == 0, "dgl_fc_dgrad: buffers must be 16-byte aligned");
+    return dgl_fc_dgrad(dgpre, wp, a2h, coef, st2, N, K, dz2h, (hipStream_t)stream);
 }
 
 // STEP_DGL_LEGACY_BN=1 in the environment keeps the three-pass BatchNorm backward (A/B measurements, debugging)
@@ -1031,15 +1054,7 @@ static int dgl_global_backward_impl(const float* series_nt, int N, int T, const 
         if (do_mid) {
             bn2_fused_coef_kernel<<<1, 64, 0, st>>>(dots, st2, p->bn2_w, count2, grads->bn2_w, grads->bn2_b, coef);
             STEP_LAUNCH_CHECK("bn2_fused_coef");
-            // dz2 = BatchNorm2 backward of dgpre @ fc_w, masked by conv2's ReLU: the scale rides in wp, the rest in the epilogue; bf16 rows out
-            // (round 4: a column-strip kernel over all rows -- wp's slice as register-resident fragments, the gradient as pre-packed
-            //  fragments, 1.6 instead of 4.7 B of operand traffic per output element -- was measured and is NOT faster than this tiled GEMM:
-            //  16.38 vs 16.33 ms at 4096 nodes, 5.99 vs 5.92 at PEMS07, profiles/r04_l_fc_dgrad_strips_ab.log)
-            StepGemm gm = gemm_desc(N, (int)K, EMB, dgpre, EMB, 1, wp, K, 1, d_a2, K);
-            gm.b_bf16 = 1;
-            gm.compute_bf16 = 1;
-            GemmFused fu = {nullptr, nullptr, a2, coef, st2, 16, T2, GEMM_FUSED_INTERLEAVED};
-            STEP_TRY(step_gemm_launch_fused(gm, fu, st));
+            STEP_TRY(dgl_fc_dgrad(dgpre, wp, a2, coef, st2, N, K, d_a2, st));
             STEP_TRY(dgl_conv2_wgrad_cl(d_a2, a1, wg_scratch, graw, N, T1, st));
         }
         if (do_tail) {

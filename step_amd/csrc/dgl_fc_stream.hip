@@ -1,12 +1,14 @@
-// Streaming kernels for the two fc products of the graph learner that have one short side (100 outputs) over a2h, the channels-last
-// bf16 conv2 activation [N][16 (T - 18)] (133 MB at PEMS04):
+// Streaming kernels for the three fc products of the graph learner, which all have one short side (100 outputs) over a2h, the
+// channels-last bf16 conv2 activation [N][16 (T - 18)] (133 MB at PEMS04):
 //   forward          gpre[N][100]  += a2h[N][K] . wp[100][K]^T
 //   weight gradient  G[100][K]      = bf16(dgpre)^T[100][N] . a2h[N][K]
+//   input gradient   dz2h[N][K]     = BatchNorm2 backward and ReLU mask (x = a2h) of bf16(dgpre)[N][100] . wp[100][K]
 // The staged GEMM keeps one k step of loads in flight per workgroup and re-reads the short operand per 128-row tile; both products ran at a
 // third of the memory system's rate.  Here a2h goes global -> LDS by DMA (lds_dma.h) through a ring of stages: a workgroup keeps two (forward)
 // or three (weight gradient) stages of loads in flight while it multiplies another, waits with a counted s_waitcnt vmcnt(n) and a raw
 // s_barrier (a __syncthreads() would drain the ring: it waits for vmcnt(0)), and reads every byte of a2h once.
-// STEP_DGL_FC_STREAM=0 (dgl.hip) keeps the staged GEMM; measurements in profiles/dgl_fc_stream_{before,after}.md.
+// STEP_DGL_FC_STREAM=0 (dgl.hip) keeps the staged GEMM; measurements in profiles/dgl_fc_stream_{before,after}.md and
+// profiles/dgl_fc_dgrad_{before,after}.md.
 #include "common.h"
 #include "step_internal.h"
 #include "lds_dma.h"
@@ -22,6 +24,7 @@ __device__ __forceinline__ void fs_wait_vm() {
     else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else if constexpr (N == 20) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
     else if constexpr (N == 40) asm volatile("s_waitcnt vmcnt(40)" ::: "memory");
+    else if constexpr (N == 53) asm volatile("s_waitcnt vmcnt(53)" ::: "memory");
     else static_assert(N == 0, "add the case");
 }
 __device__ __forceinline__ void fs_barrier() {
@@ -269,6 +272,156 @@ __global__ __launch_bounds__(WG_THREADS) void fc_stream_wgrad_kernel(const uint1
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Input gradient with BatchNorm2's backward and conv2's ReLU mask: dz2h[n][k'] = x > 0 ? v - km1 - (x - mu) km2 : 0 with
+// v = bf16(dgpre)[n][.] . wp[.][k'], x = a2h[n][k'] and the per-channel km1 / km2 / mu of the staged GEMM's interleaved epilogue
+// (gemm_bf16.hip, GEMM_FUSED_INTERLEAVED): the contraction is the short side (100 outputs, 7 products of 16), the launch is an epilogue
+// over a2h / dz2h with a small product in front of it.  A workgroup owns one row tile of DG_TM = 320 nodes and a contiguous range of
+// column tiles of 64 bf16; math wave w (of 5) owns rows 64 w .. + 63 and keeps bf16(dgpre) of them (round to nearest even, zero past
+// O) as 14 fragments in registers for the life of the workgroup.  A stage is the forward kernel's: 320 a2h rows + 104 wp rows of 128
+// bytes, 53 DMA instructions, through a ring of three.  The SIXTH wave issues every DMA and does the counted waits (see the weight
+// gradient: a wave's stores share vmcnt with its loads).  vmcnt counts to 63, so of the two stages the ring runs ahead about 63 KB per
+// unit are in flight at a time -- several times what one unit's share of the memory rate needs.
+//   wp    : the matrix operand wants 8 consecutive o of one column per lane: ds_read_b64_tr_b16 from the row-major image [o][64].  At a
+//           128-byte pitch rows q and q + 2 of the 4 rows x 64 bytes that 32 lanes read share their banks: the two 64-byte halves of rows
+//           2, 3 (mod 4) are exchanged (piece c in slot c ^ 4 ((o >> 1) & 1), through the source addresses), and the four rows cover all
+//           64 banks once.  The seventh product's upper half (o = 104 .. 111) reads rows 96 .. 103 again: finite values against zeros.
+//   a2h   : is not a matrix operand but the epilogue's x, swizzled like the forward's (piece c of row r in slot c ^ (r & 7): an
+//           accumulator register's 32 columns x 2 rows, four rows apart, hit 32 different banks).  A lane reads x at its accumulator
+//           coordinates and writes the bf16 result IN PLACE; a wave's 64 rows are its own, so without a workgroup barrier it then moves
+//           them out as whole 16-byte pieces, 128-byte runs per row.  The stage is refilled after the next barrier: its data has left LDS
+//           by then (the stores take their data from registers).
+// The products are those of the staged GEMM (the same instruction, dgpre as its first operand, o ascending) and the epilogue is its
+// expression: the result is bit-identical to it.  Rows past N repeat row N - 1, pieces past K the row's first piece of the tile; neither
+// is stored.
+constexpr int DG_TM = FS_TM, DG_CT = FS_KS, DG_ROWB = FS_ROWB, DG_WROWS = FS_WROWS, DG_RING = FS_RING, DG_STAGE = FS_STAGE;
+constexpr int DG_MATH_WAVES = DG_TM / 64, DG_THREADS = (DG_MATH_WAVES + 1) * 64, DG_OMAX = 100, DG_KB = (DG_OMAX + 15) / 16;
+constexpr int DG_LOADS = (DG_TM + DG_WROWS) / 8;
+static_assert(DG_LOADS <= 63 && DG_WROWS % 8 == 0 && DG_WROWS >= 16 * (DG_KB - 1) + 8 && DG_RING * DG_STAGE <= 160 * 1024, "input-gradient stage");
+
+__global__ __launch_bounds__(DG_THREADS) void fc_stream_dgrad_kernel(const float* __restrict__ D, const uint16_t* __restrict__ W,
+                                                                     const uint16_t* __restrict__ A, const float* __restrict__ coef,
+                                                                     const float* __restrict__ st2, int N, int O, long K, int per, int rtiles,
+                                                                     uint16_t* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char fs_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int rt = blockIdx.x % rtiles, s = blockIdx.x / rtiles;      // the row tiles of a column range are neighbours: they share its wp
+    const int row0 = rt * DG_TM;
+    const int tiles = (int)((K + DG_CT - 1) / DG_CT);
+    const int tile0 = s * per;
+    const int ntile = min(tiles - tile0, per);
+    if (ntile <= 0) return;
+    if (wave == DG_MATH_WAVES) {
+        const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)fs_lds;
+        // lane -> row lane >> 3 of an 8-row group, slot lane & 7; the piece that belongs there (see above)
+        const int pca = (lane & 7) ^ (lane >> 3), pcw = (lane & 7) ^ (((lane >> 4) & 1) << 2);
+        auto issue = [&](int tile, int buf) {
+            const long c0 = (long)(tile0 + tile) * DG_CT;
+            const long offa = c0 + (c0 + pca * 8 < K ? pca * 8 : 0), offw = c0 + (c0 + pcw * 8 < K ? pcw * 8 : 0);
+            const uint32_t base = lds0 + (uint32_t)(buf * DG_STAGE);
+#pragma unroll
+            for (int j = 0; j < DG_TM / 8; ++j)
+                lds_dma_1k(A + (long)min(row0 + j * 8 + (lane >> 3), N - 1) * K + offa, base + (uint32_t)(j * 1024));
+#pragma unroll
+            for (int j = 0; j < DG_WROWS / 8; ++j)
+                lds_dma_1k(W + (long)min(j * 8 + (lane >> 3), O - 1) * K + offw, base + (uint32_t)(DG_TM * DG_ROWB + j * 1024));
+        };
+        issue(0, 0);
+        if (ntile > 1) issue(1, 1);
+        for (int i = 0; i < ntile; ++i) {
+            // stage i has landed when at most the loads of stage i + 1 are still in flight
+            if (i + 1 < ntile) fs_wait_vm<DG_LOADS>(); else fs_wait_vm<0>();
+            fs_barrier();                                              // stage i is there; the math waves have moved stage i - 1 out
+            if (i + 2 < ntile) issue(i + 2, (i + 2) % DG_RING);        // ... whose buffer is refilled
+        }
+        return;
+    }
+    const int r = lane & 31, h = lane >> 5;
+    // this wave's 64 rows of bf16(dgpre) stay in registers: 2 x 7 fragments of 16 outputs
+    bf16x8 afr[2][DG_KB];
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2) {
+        const float* d = D + (long)min(row0 + wave * 64 + t2 * 32 + r, N - 1) * O;
+#pragma unroll
+        for (int kb = 0; kb < DG_KB; ++kb) {
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int o = kb * 16 + 8 * h + j;
+                const float x = d[min(o, O - 1)];
+                v[j] = o < O ? x : 0.f;
+            }
+            afr[t2][kb] = pack8(v);
+        }
+    }
+    const int c = lane & 15;                                           // a column tile starts at a multiple of 64: one channel per lane
+    const float km1 = coef[32 + c] * coef[c], km2 = coef[32 + c] * coef[16 + c] * st2[48 + c], mu = st2[32 + c];
+    // transposed reads of wp: 16-lane group g covers columns 16 (g & 1) .. + 15, lane 4 q + p of it row q, columns 4 p .. + 3
+    const int q = (lane & 15) >> 2, qb = (q >> 1) & 1;
+    int trw[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) trw[j] = DG_TM * DG_ROWB + q * DG_ROWB + (j ^ qb) * 64 + ((lane >> 4) & 1) * 32 + (lane & 3) * 8;
+    // x / result of accumulator register e: row 8 (e >> 2) + (e & 3) + 4 h of a 32 x 32 tile, column lane & 31
+    int xoff[4][2];
+#pragma unroll
+    for (int e3 = 0; e3 < 4; ++e3)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int r7 = e3 + 4 * h;
+            xoff[e3][j] = (wave * 64 + r7) * DG_ROWB + (((j * 4 + (r >> 3)) ^ r7) << 4) + (r & 7) * 2;
+        }
+    const int pc = (lane & 7) ^ (lane >> 3);                           // the piece in slot lane & 7 of row lane >> 3 (mod 8)
+    for (int i = 0; i < ntile; ++i) {
+        fs_barrier();
+        char* buf = fs_lds + (i % DG_RING) * DG_STAGE;
+        f32x16 acc[4];
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+#pragma unroll
+        for (int kb = 0; kb < DG_KB; ++kb) {
+            const int rowb = 16 * kb + 8 * h < DG_WROWS ? 16 * kb + 8 * h : 16 * kb;
+            bf16x8 b[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const char* p = buf + rowb * DG_ROWB + trw[j];
+                const u32x2 lo = fs_read_tr(p), hi = fs_read_tr(p + 4 * DG_ROWB);
+                const u32x4 t = {lo[0], lo[1], hi[0], hi[1]};
+                b[j] = __builtin_bit_cast(bf16x8, t);
+            }
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0][kb], b[0], acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[0][kb], b[1], acc[1], 0, 0, 0);
+            acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[1][kb], b[0], acc[2], 0, 0, 0);
+            acc[3] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(afr[1][kb], b[1], acc[3], 0, 0, 0);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            // all 16 reads of a tile before its first write: the compiler cannot reorder a read over a write that may alias it
+            uint16_t xb[16];
+#pragma unroll
+            for (int e = 0; e < 16; ++e) xb[e] = *(const uint16_t*)(buf + ((t >> 1) * 32 + 8 * (e >> 2)) * DG_ROWB + xoff[e & 3][t & 1]);
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const float x = __uint_as_float((uint32_t)xb[e] << 16);
+                const float v = acc[t][e];
+                const float o = x > 0.f ? v - km1 - (x - mu) * km2 : 0.f;
+                *(uint16_t*)(buf + ((t >> 1) * 32 + 8 * (e >> 2)) * DG_ROWB + xoff[e & 3][t & 1]) = __builtin_bit_cast(uint16_t, (__bf16)o);
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // the wave's own rows: LDS serves a wave in order
+        const long col = (long)(tile0 + i) * DG_CT + pc * 8;
+        uint4 piece[8];
+#pragma unroll
+        for (int it = 0; it < 8; ++it) piece[it] = *(const uint4*)(buf + (wave * 64 + it * 8 + (lane >> 3)) * DG_ROWB + (lane & 7) * 16);
+#pragma unroll
+        for (int it = 0; it < 8; ++it) {
+            const int row = row0 + wave * 64 + it * 8 + (lane >> 3);
+            if (row < N && col < K) *(uint4*)(out + (long)row * K + col) = piece[it];
+        }
+    }
+}
+
 int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
     return e && e[0] ? atoi(e) : dflt;
@@ -320,5 +473,35 @@ int dgl_fc_stream_wgrad(const void* a2h, const float* dgpreT, int N, int O, long
     STEP_TRY(step_raise_lds_once((const void*)fc_stream_wgrad_kernel, 160 * 1024, "dgl_fc_stream_wgrad"));
     fc_stream_wgrad_kernel<<<(tiles + per - 1) / per, WG_THREADS, WG_DBYTES + WG_RING * WG_STAGE, st>>>((const uint16_t*)a2h, dgpreT, N, O, K, per, G);
     STEP_LAUNCH_CHECK("dgl_fc_stream_wgrad");
+    return STEP_OK;
+}
+
+// Up to three row tiles (STEP_PEMS07's 883 nodes) the step is faster on the kernel; at 4096 nodes (13 row tiles) the launch takes what the
+// staged GEMM takes (1366 against 1375 us) and the step measured slower, so larger graphs keep the staged GEMM
+// (profiles/dgl_fc_dgrad_after.md; nothing between 883 and 4096 nodes was measured).
+constexpr int DG_MAX_RTILES = 3;
+bool dgl_fc_stream_dgrad_ok(int N, long K) { return N > 0 && N <= DG_MAX_RTILES * DG_TM && K > 0; }
+
+// dz2h [N][K] (bf16) = BatchNorm2 backward + conv2 ReLU mask of bf16(dgpre)[N][O] . wp[O][K] (wp, a2h bf16; K a multiple of 16): what the
+// staged GEMM's GEMM_FUSED_INTERLEAVED epilogue stores, bit for bit.  At most one workgroup per unit: DG_GROUPS column ranges spread over
+// the row tiles.  (STEP_PEMS07 queues the next batch's encoder late, so it runs next to the backward on 128 units; 128 workgroups were
+// measured there against 256 and are within the run-to-run range: 5.106 / 5.184 / 5.187 against 5.151 / 5.159 / 5.122 ms per step.)
+// STEP_DGL_FC_STREAM_DGROUPS (read on every call) overrides it for measurements.
+constexpr int DG_GROUPS = 256;
+int dgl_fc_stream_dgrad(const float* dgpre, const void* wp, const void* a2h, const float* coef, const float* st2, int N, int O, long K,
+                        void* dz2h, hipStream_t st) {
+    STEP_REQUIRE(dgpre && wp && a2h && coef && st2 && dz2h && N > 0 && O > 0 && O <= DG_OMAX && K > 0 && K % 16 == 0,
+                 "dgl_fc_stream_dgrad: bad arguments");
+    STEP_REQUIRE(((((uintptr_t)wp) | ((uintptr_t)a2h) | ((uintptr_t)dz2h)) & 15) == 0, "dgl_fc_stream_dgrad: wp, a2h and dz2h must be 16-byte aligned");
+    const int tiles = (int)((K + DG_CT - 1) / DG_CT), rtiles = cdiv(N, DG_TM);
+    int ranges = env_int("STEP_DGL_FC_STREAM_DGROUPS", DG_GROUPS) / rtiles;
+    if (ranges > tiles) ranges = tiles;
+    if (ranges < 1) ranges = 1;
+    const int per = (tiles + ranges - 1) / ranges;
+    const int used = (tiles + per - 1) / per;                          // ranges that hold at least one tile
+    STEP_TRY(step_raise_lds_once((const void*)fc_stream_dgrad_kernel, 160 * 1024, "dgl_fc_stream_dgrad"));
+    fc_stream_dgrad_kernel<<<used * rtiles, DG_THREADS, DG_RING * DG_STAGE, st>>>(dgpre, (const uint16_t*)wp, (const uint16_t*)a2h, coef, st2, N, O, K, per,
+                                                                                 rtiles, (uint16_t*)dz2h);
+    STEP_LAUNCH_CHECK("dgl_fc_stream_dgrad");
     return STEP_OK;
 }

@@ -82,6 +82,9 @@ int dgl_conv1_wgrad_mfma(const float* dz, const float* x, float* scratch, float*
 int dgl_fc_stream_fwd(const void* a2h, const void* wp, int N, int O, long K, float* gpre, float* ws, long ws_floats, hipStream_t st);
 bool dgl_fc_stream_wgrad_ok(int N);
 int dgl_fc_stream_wgrad(const void* a2h, const float* dgpreT, int N, int O, long K, float* G, hipStream_t st);
+bool dgl_fc_stream_dgrad_ok(int N, long K);
+int dgl_fc_stream_dgrad(const float* dgpre, const void* wp, const void* a2h, const float* coef, const float* st2, int N, int O, long K,
+                        void* dz2h, hipStream_t st);
 int step_colsum_launch(const float* x, long rows, int cols, long ld, float* out, hipStream_t st);
 
 // Fork / join of leaf work onto a second stream (events from a per-thread, per-device pool): the data-gradient chain of a backward

@@ -32,18 +32,17 @@ def rows_of(N, T, B, P, L):
     hop_key = ("gemm_fast_kernelILi128ELi64ELi1ELi2ELb0", "gemm_fast_kernelILi64ELi64ELi1ELi2ELb0")
     return [
         ("tsformer_encoder_kernel", f"fused TSFormer encoder ({S} sequences x {P} tokens)", "mfma", S * L * 4 + S * P * 96 * 2, S * P * (4 * (221184 + 384 * P) + 2304)),
-        # (graphs of up to 320 nodes: the cosine Gram is gram_sym_kernel + gram_finish_kernel since round 6, and this instantiation is the fc forward alone)
-        (("gemm_fast_kernelILi128ELi128ELi1ELi1ELb0",) if N > 320 else ("gemm_fast_kernelILi128ELi128ELi1ELi1ELb0",),
-         (f"cosine Gram ({B} x {N}^2 x {P * 96}) and DGL fc forward (bf16 rows x bf16 weight copy), averaged" if N > 320 else
-          "DGL fc forward (bf16 rows x bf16 weight copy, split-K through a workspace)"), "hbm/L2",
-         (S * P * 96 * 2 + B * N * N * 4 + a2h + wp) / 2 if N > 320 else a2h + wp, (2.0 * B * N * N * P * 96 + 2.0 * N * EMB * K) / 2 if N > 320 else 2.0 * N * EMB * K),
+        # (the fc forward streams through dgl_fc_stream.hip; above 320 nodes this instantiation of the staged GEMM is the cosine Gram alone, below it
+        #  is not launched: the Gram is gram_sym_kernel + gram_finish_kernel since round 6)
+        ("gemm_fast_kernelILi128ELi128ELi1ELi1ELb0", f"cosine Gram ({B} x {N}^2 x {P * 96}) on the staged GEMM", "hbm/L2", S * P * 96 * 2 + B * N * N * 4, 2.0 * B * N * N * P * 96),
+        ("fc_stream_fwd_kernel", "DGL fc forward (streaming kernel: a2h and the bf16 weight copy once through an LDS-DMA ring, k ranges through a workspace)", "hbm", a2h + wp, 2.0 * N * EMB * K),
         ("gram_sym_kernel", f"symmetric cosine Gram ({B} x {N}^2 x {P * 96}): the whole output per workgroup, H read once, blocks on / above the diagonal", "mfma/lds",
          S * P * 96 * 2 + B * N * N * 4, 2.0 * B * N * N * P * 96),
         ("gram_finish_kernel", "sum of the Gram product's feature slices + cosine normalisation, both triangles", "hbm", 16 * B * ((N + 63) // 64) * ((N + 63) // 64 + 1) // 2 * 16384 + B * N * N * 4, None),
-        ("gemm_fast_kernelILi128ELi128ELi2ELi3ELb0", "DGL fc weight gradient G = dgpre^T a2 (n-contiguous bf16 loader)", "hbm", a2h + fcw, 2.0 * N * EMB * K),
+        (("fc_stream_wgrad_kernel", "gemm_fast_kernelILi128ELi128ELi2ELi3ELb0"), "DGL fc weight gradient G = dgpre^T a2 (streaming kernel up to 320 nodes, staged GEMM above)", "hbm", a2h + fcw, 2.0 * N * EMB * K),
         ("fc_unpermute_kernel", "G -> fc.weight layout, BN2 affine, stored into the gradient, BN2 backward sums", "hbm", 3 * fcw, None),
         ("fc_prep_kernel", "per-step bf16 (t,c)-ordered copy of fc.weight with BN2's scale", "hbm", fcw + wp, None),
-        ("gemm_fast_kernelILi128ELi128ELi0ELi3ELb0ELb0ELb1", "DGL fc input gradient + fused BN2 backward / ReLU mask (reads a2h, writes dz2h)", "hbm", wp + 2 * a2h, 2.0 * N * EMB * K),
+        (("fc_stream_dgrad_kernel", "gemm_fast_kernelILi128ELi128ELi0ELi3ELb0ELb0ELb1"), "DGL fc input gradient + fused BN2 backward / ReLU mask (reads a2h, writes dz2h; streaming kernel up to 960 nodes, staged GEMM above)", "hbm", wp + 2 * a2h, 2.0 * N * EMB * K),
         ("conv1_fwd_cl_kernel", "DGL conv1 forward (series -> a1h)", "hbm", N * T * 4 + a1h, 2.0 * N * T1 * 8 * 10),
         ("conv2_fwd_cl_kernel", "DGL conv2 forward (a1h -> a2h)", "hbm", a1h + a2h, 2.0 * N * T2 * 16 * 80),
         ("conv2_dgrad_cl_kernel", "DGL conv2 input gradient + fused BN1 backward (dz2h, a1h -> dz1h)", "hbm", a2h + 2 * a1h, 2.0 * N * T2 * 16 * 80),
