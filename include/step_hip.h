@@ -593,6 +593,32 @@ int step_eval_metrics_accumulate_nodes(const float* pred, long p_sb, long p_sh, 
                                        void* stream);
 int step_eval_metrics_finish(const double* acc, int H, double* out, void* stream);
 
+/* ---------------------------------------------------------------- per-node evaluation metrics
+ * The same pass per sensor: the five sums of the evaluation metrics above kept per (horizon, node), and, optionally, the rescaled
+ * prediction of every element stored as it is taken -- what a caller otherwise gets from keeping every prediction and looping over N
+ * slices on the host (csrc/eval_nodes.hip; additive to ABI 10).  Issued NEXT TO step_eval_metrics_accumulate on the same views; the
+ * element terms (two roundings of x * scale + shift, the masks, the MAPE rule, a NaN term adds 0 and still counts) are the same.
+ *  pred, real   as above: f32 views [B, H, N] by ELEMENT strides, normalised
+ *  table        f64 [5, H, N] = step_eval_node_table_doubles(H, N) doubles, struct-of-arrays: sum k of {S_abs, S_sq, cnt, S_ape, cnt0}
+ *               of horizon h and node n at (k * H + h) * N + n, over every window of every call since the CALLER zeroed it.  A slot has
+ *               one writer per launch (plain load, add, store; no atomics): calls on one table must be ordered by their stream, and the
+ *               sums depend on neither grid nor timing.  Every slot is a sum of per-call terms, so tables of several ranks merge by
+ *               addition.  May be NULL (the export alone; real is then not read)
+ *  out          f32 [B, H, N] contiguous, or NULL: element (b, h, n) receives pred * scale + shift, rounded twice -- the value the
+ *               metrics are taken on, torch's `pred * std + mean` to the bit (NaN included).  table and out must not both be NULL
+ *  _nodes       the per-node scaler of step_eval_metrics_accumulate_nodes: scale_n, shift_n f32 [N] on the device
+ *  _finish      out f64 [H + 1, N, 3]: {MAE, RMSE, MAPE} of node n at horizon h at ((h * N) + n) * 3 for h < H; row H holds the node's
+ *               metrics over all horizons, from its sums added over h.  A count of 0 gives 0.  table is left as it is
+ * H <= 64, B * N < 2^31, null_val not infinite.  One launch per call. */
+long step_eval_node_table_doubles(int H, int N);          /* 5 * H * N; 0 for H < 1, H > 64 or N < 1; pure host function */
+int step_eval_node_metrics_accumulate(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh, long r_sn,
+                                      int B, int H, int N, float scale, float shift, float null_val, double* table, float* out,
+                                      void* stream);
+int step_eval_node_metrics_accumulate_nodes(const float* pred, long p_sb, long p_sh, long p_sn, const float* real, long r_sb, long r_sh,
+                                            long r_sn, int B, int H, int N, const float* scale_n, const float* shift_n, float null_val,
+                                            double* table, float* out, void* stream);
+int step_eval_node_metrics_finish(const double* table, int H, int N, double* out, void* stream);
+
 /* ---------------------------------------------------------------- training tail -----------
  * The tail of one training iteration in two launches: the loss of step/step_loss/step_loss.py:5-16 on the first k horizon steps of the
  * RESCALED prediction and label (curriculum learning, basicts/runners/base_tsf_runner.py:170-190, 243-246), both of its gradients, and

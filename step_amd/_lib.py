@@ -171,6 +171,11 @@ _SIGS = {
     "step_eval_metrics_accumulate": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _f, _f, _f, _vp, _vp]),
     "step_eval_metrics_accumulate_nodes": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _vp, _vp, _f, _vp, _vp]),
     "step_eval_metrics_finish": (_i, [_vp, _i, _vp, _vp]),
+    # the same pass per (horizon, node), and the predictions in data units (csrc/eval_nodes.hip)
+    "step_eval_node_table_doubles": (_l, [_i, _i]),
+    "step_eval_node_metrics_accumulate": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _f, _f, _f, _vp, _vp, _vp]),
+    "step_eval_node_metrics_accumulate_nodes": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _vp]),
+    "step_eval_node_metrics_finish": (_i, [_vp, _i, _i, _vp, _vp]),
     # loss, gradients and meters of a training iteration on the first k horizons (csrc/train_tail.hip)
     "step_train_tail_work_doubles": (_l, []),
     "step_train_tail": (_i, [_vp, _l, _l, _l, _vp, _l, _l, _l, _i, _i, _i, _i, _f, _f, _f, _vp, _vp, _l, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -8,7 +8,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libstep_hip.so")
 SOURCES = ["errors.cpp", "comm.cpp", "gemm.hip", "gemm_bf16.hip", "tsformer_encoder.hip", "knn.hip", "selftest.hip",
            "dgl.hip", "dgl_conv_mfma.hip", "dgl_fc_stream.hip", "gwnet.hip", "optim.hip", "pretrain.hip", "pretrain_fused.hip", "pretrain_attn2.hip",
-           "eval_cache.hip", "eval_metrics.hip", "train_tail.hip", "pretrain_tail.hip", "replica_digest.hip"]
+           "eval_cache.hip", "eval_metrics.hip", "eval_nodes.hip", "train_tail.hip", "pretrain_tail.hip", "replica_digest.hip"]
 
 
 def _newer(target, deps):

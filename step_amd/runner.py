@@ -367,7 +367,7 @@ class _Deferred:
 def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, encoder_workgroups=None, native_metrics=True,
                   eval_cache_bytes=0, native_tail=False, native_pretrain=False, native_data_parallel=False, replica_check=True,
                   native_eval=False, eval_batch_size=None, accumulate=1, shard_graph_learner=False, eval_noise="position",
-                  native_test=False, spread_eval=False):
+                  native_test=False, spread_eval=False, test_per_node=False):
     """-> subclass of ``base`` (the reference's ``STEPRunner``, or any ``BaseTimeSeriesForecastingRunner``) for ``CFG.RUNNER``.
     ``encoder_workgroups``: compute units of the persistent encoder launch next to the step (None: 160 at 307 nodes / 336 tokens, the
     measured optimum of config C2; 0: one workgroup per sequence) -- only used while batches are prefetched.
@@ -463,7 +463,13 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
     ``eval_noise="window"`` in effect -- only then is a pass the same whoever evaluates which batch.  Rank 0's eval seed is broadcast
     once.  With ``shard_graph_learner`` acting the passes run behind the gather of the slices.  A validation forward whose outputs
     do not qualify for ``EvalMetrics`` raises instead of taking the torch path (the other ranks would wait in the collective).
-    Without ``native_data_parallel``, or in a single process, the switch does nothing."""
+    Without ``native_data_parallel``, or in a single process, the switch does nothing.
+    ``test_per_node``: with ``native_test`` acting, the test pass's ``EvalMetrics`` is built with ``nodes=`` the model's node count (on
+    every rank of a spread pass, also one without a batch: all ranks reduce the same number of doubles), rank 0 keeps the pass's
+    ``EvalResult`` -- ``per_node`` [N, H, 3] and ``per_node_overall`` [N, 3] filled -- as ``self.test_result`` and logs ONE more line
+    behind the reference's per-horizon lines: the five sensors with the largest overall MAE and their values.  The lines, the three
+    ``test_`` meters and the single read-back of the pass are as without it.  Where ``native_test`` is not in effect the switch does
+    nothing and rank 0 warns once.  The validation meters and the pre-training stage have no per-sensor tables.  Off by default."""
     import operator
     if eval_noise not in ("position", "window"):
         raise ValueError(f"native_runner: eval_noise must be \"position\" or \"window\", got {eval_noise!r}")
@@ -487,6 +493,8 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             self._spread_acting = False          # spread_eval: the validation / test passes are spread over the ranks
             self._helper_loaders = {}          # ... on a rank other than 0: its own "val" / "test" loaders
             self.eval_readbacks = 0          # device-to-host copies of EvalMetrics tables (one per pass)
+            self.test_result = None          # test_per_node: the EvalResult of the last native test pass (rank 0)
+            self._per_node_warned = False
             self._group_size, self._group_pos = 1, 0          # accumulate: size of the open group, iterations of it that ran backward
 
         # ---------------------------------------------------------------- loaders
@@ -979,6 +987,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             if self._pretrain_module() is None:
                 scaler = self._eval_conditions() if native_test else None
                 if scaler is None:
+                    self._per_node_without_native_test()
                     return super().test(*args, **kwargs)
                 if self._rank_world()[0] != 0:
                     return None          # (the reference's test() is master_only; the other ranks of a spread pass: _helper_passes)
@@ -1000,6 +1009,13 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                     data = next(batches, None)
             return None
 
+        def _per_node_without_native_test(self):
+            if test_per_node and not self._per_node_warned and self._rank_world()[0] == 0:
+                import warnings
+                self._per_node_warned = True
+                warnings.warn("step_amd.runner: test_per_node needs native_test in effect (a STEP on a GPU, the re_standard_transform "
+                              "scaler, only the three basicts metrics, a real null_val); the test pass has no per-sensor table")
+
         # ---------------------------------------------------------------- the forecasting test pass on the device (native_test=True)
         def _native_test(self, scaler, loader, base_test=None):
             """base_tsf_runner.py:277-318 from one ``EvalMetrics``: one accumulate launch per batch on the normalised prediction and the
@@ -1009,6 +1025,7 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
             from .evaluate import EvalMetrics
             mean, std = scaler
             rank = self._rank_world()[0]
+            nodes = int(_unwrap(self.model).backend.num_nodes) if test_per_node else None
             m = None
             with torch.no_grad():
                 for data in loader:
@@ -1016,16 +1033,18 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                     pred, real = forward_return[0], forward_return[1]
                     if not (self._qualifies(pred, real) and self._scaler_fits(scaler, pred)):
                         if m is None and base_test is not None and not self._spread_acting:
+                            self._per_node_without_native_test()
                             return base_test()
                         raise RuntimeError("step_amd.runner: native_test met a forward whose outputs EvalMetrics cannot take "
                                            f"(prediction {tuple(getattr(pred, 'shape', ()))}, {getattr(pred, 'dtype', type(pred))})")
                     if m is None:
-                        m = EvalMetrics(pred.shape[1], float(self.null_val), rescale=(std, mean), device=pred.device)
+                        m = EvalMetrics(pred.shape[1], float(self.null_val), rescale=(std, mean), device=pred.device, nodes=nodes)
                     m.update(pred, real)
             if self._spread_acting:
                 if m is None and loader.total_batches() > 0:          # a rank without a batch of its own still answers the collective
                     H = int(getattr(loader.dataset, "future_len", 12))
-                    m = EvalMetrics(H, float(self.null_val), rescale=(std, mean), device=next(_unwrap(self.model).parameters()).device)
+                    m = EvalMetrics(H, float(self.null_val), rescale=(std, mean), device=next(_unwrap(self.model).parameters()).device,
+                                    nodes=nodes)
                 if m is not None:
                     m.all_reduce(_unwrap(self.model)._process_group)          # the pass's one collective
             if m is None or rank != 0:
@@ -1039,6 +1058,12 @@ def native_runner(base, prefetch=True, defer_meters=True, fused_optimizer=True, 
                     metric_repr += ", Test {0}: {1:.4f}".format(metric_name, float(res.per_horizon[i][k]))
                 log = "Evaluate best model on test data for horizon {:d}" + metric_repr
                 self.logger.info(log.format(i + 1))
+            if test_per_node:
+                self.test_result = res
+                mae = res.per_node_overall[:, 0]
+                worst = sorted(range(len(mae)), key=lambda n: (-mae[n], n))[:5]
+                self.logger.info("Test MAE per sensor over all horizons, the largest (sensor: MAE): "
+                                 + ", ".join("{:d}: {:.4f}".format(n, float(mae[n])) for n in worst))
             for metric_name, k in names:
                 super().update_epoch_meter("test_" + metric_name, float(res.overall[k]))
             return None

@@ -1253,10 +1253,12 @@ class STEP(nn.Module):
 
     # ------------------------------------------------------------------ validation / test pass
     def evaluate(self, loader, origins=None, scaler=None, null_val=0.0, batch_size=None, target_channel=0, horizons=None,
-                 return_predictions=False, process_group=None):
+                 return_predictions=False, process_group=None, per_node=False):
         """One validation / test pass over a device-resident series with the reference's masked MAE / RMSE / MAPE per horizon, overall
         and per batch accumulated on the device and read back once: ``step_amd.evaluate.evaluate_pass`` (documented there).
-        ``process_group``: the pass spread over the ranks of a ``torch.distributed`` group (needs ``eval_noise == "window"``)."""
+        ``process_group``: the pass spread over the ranks of a ``torch.distributed`` group (needs ``eval_noise == "window"``).
+        ``per_node=True``: the same three metrics per sensor as well (``EvalResult.per_node`` / ``per_node_overall``);
+        ``return_predictions="data"``: the kept predictions in the data's units, stored by the per-node kernel."""
         from ..evaluate import evaluate_pass
         return evaluate_pass(self, loader, origins, scaler=scaler, null_val=null_val, batch_size=batch_size, target_channel=target_channel,
-                             horizons=horizons, return_predictions=return_predictions, process_group=process_group)
+                             horizons=horizons, return_predictions=return_predictions, process_group=process_group, per_node=per_node)
